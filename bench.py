@@ -6,7 +6,12 @@ tensors, 25,610,152 elements) client updates per GPU, top-k ratio 0.01, 8-bit co
 encode all 16 + decode all 16. Weak scaling: every rank does its own share (clients are independent; no
 collective on the data path — torch.distributed only for the barrier and the max-over-ranks of the time).
 
-`configs` extras, each timed the same way on the same GPU:
+A plain run sets up the headline workload, warms it up, times the K steps, writes its outputs if --dump-outputs
+is given and prints the result line (metric, value, unit, ms_per_step, ...). Everything below — the `configs`
+extras, the per-kernel roofline, the repeat windows, the device copy probe and the CPU baseline — runs only with
+--full and adds its keys to the same line.
+
+`configs` extras (--full), each timed the same way on the same GPU:
   C2      16 x ResNet-18 (CIFAR-10, 11,183,562 elements) per GPU
   C4      16 x ViT-B/16 (86,567,656 elements) per GPU (C4 is 128 clients on 8 GPUs)
   C5      one GPU's share of the heterogeneous splitFL round (256 clients, greedy-grouped over 8 GPUs:
@@ -37,7 +42,13 @@ cpu_baseline: the numpy oracle (oracle/codec_oracle.py) on a bounded sample of t
 host's cores (a process pool, timed before the GPU is touched), plus its single-thread rate and the
 reference's current boundary (identity pickle of the state, coala/protocol/codec.py:4-9); rank 0, N = 1.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--extras C2,C4,C5,single|none]
+--dump-outputs DIR: after the timed steps, what the last timed step of the headline workload returned to its
+caller (the Encoded buffers idx / vals / mn / scale / ustart and the decoded dense buffer) as DIR/<name>.npy,
+float32 or float64 (8-bit codes as float32, int32 arrays as float64: exact), at most DUMP_CAPS elements each (larger arrays: a fixed, seeded
+sample of positions; under 64 MB in all). The inputs are seeded, so two builds can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR]
+                    [--full [--extras C2,C4,C5,single|none] [--no-cpu-baseline]]
 """
 import argparse
 import json
@@ -89,7 +100,13 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--config", default="C3", choices=sorted(CONFIGS), help="headline workload")
-    p.add_argument("--extras", default=DEFAULT_EXTRAS, help="comma-separated extra configs, or 'none'")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the extra configs, the per-kernel roofline "
+                        "steps, the repeat windows, the device copy probe and the CPU baseline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step of the headline workload computed as DIR/<name>.npy")
+    p.add_argument("--extras", default=None,
+                   help=f"with --full: comma-separated extra configs, or 'none' (default: {DEFAULT_EXTRAS})")
     p.add_argument("--layout", default=None, help="override the headline layout (uniform configs)")
     p.add_argument("--clients", type=int, default=None, help="override client updates per GPU")
     p.add_argument("--ratio", type=float, default=0.01)
@@ -130,7 +147,14 @@ def parse():
     p.add_argument("--launch-check-fail", type=int, default=-1,
                    help="with --launch-check: this rank exits with code 3 before joining (the others block in the "
                         "rendezvous until the launcher stops them)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if a.extras not in (None, "none") and not a.full:
+        p.error("--extras needs --full (a plain run times the headline workload only)")
+    if a.extras is None:
+        a.extras = DEFAULT_EXTRAS if a.full else "none"
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -412,7 +436,48 @@ def capture_graphs(W, a):
         torch.cuda.synchronize()
 
 
-def time_workload(W, a, dev, world):
+DUMP_SEED = 20240607  # positions of the sample --dump-outputs keeps of an array larger than its cap
+DUMP_CAPS = {"idx": 1 << 21, "vals": 1 << 21, "mn": 1 << 20, "scale": 1 << 20, "ustart": 1 << 20, "decoded": 1 << 22}
+
+
+def dump_outputs(W, a, path):
+    """--dump-outputs: the Encoded buffers and the dense output that the last timed step wrote (step K - 1: its
+    slot's buffer set, as _step picks it) as <path>/<name>.npy. float32 arrays stay float32, 8-bit codes become
+    float32 and int32 arrays float64 (both exact). `decoded` holds the segments' elements back to back, in table
+    order (the alignment pads between segments are never written, so they are left out). An array above
+    DUMP_CAPS[name] elements is sampled at sorted positions drawn from DUMP_SEED (the same positions for arrays
+    of one length, so idx and vals stay paired): 16 + 8 + 4 + 4 + 8 + 16 MiB at most."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    slots = W["slots"]
+    i = a.steps - 1
+    enc, out = slots[i % len(slots)][1][(i // len(slots)) % W["rot"]]
+
+    def positions(name, n):  # None: all of them
+        if n <= DUMP_CAPS[name]:
+            return None
+        return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_CAPS[name]))
+
+    def save(name, t):
+        x = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), x.astype(np.float32 if x.dtype in (np.float32, np.uint8) else np.float64))
+    os.makedirs(path, exist_ok=True)
+    for name in enc.FIELDS:
+        t = getattr(enc, name)
+        if t is None or t.numel() == 0:  # (the dense codec has neither idx nor ustart)
+            continue
+        pos = positions(name, t.numel())
+        save(name, t if pos is None else t[torch.from_numpy(pos).to(t.device)])
+    segs = W["table"].segs.astype(np.int64)  # rows (offset, n, k, ...)
+    cum = np.concatenate([[0], np.cumsum(segs[:, 1])])
+    pos = positions("decoded", int(cum[-1]))
+    pos = np.arange(cum[-1], dtype=np.int64) if pos is None else pos
+    row = np.searchsorted(cum, pos, side="right") - 1
+    save("decoded", out[torch.from_numpy(segs[row, 0] + pos - cum[row]).to(out.device)])
+
+
+def time_workload(W, a, dev, world, dump_dir=None):
     import torch
     import torch.distributed as dist
 
@@ -459,8 +524,26 @@ def time_workload(W, a, dev, world):
     el = timed_region()
     rank_el = gather_elapsed(el, world, dev)
     el = max(rank_el)  # the job's time: the slowest rank
+    if dump_dir:
+        dump_outputs(W, a, dump_dir)
+    N, K, T = t.n_elements, t.total_k, t.n_segments
+    delta = W["mode"] == "delta"
+    step_ms = el / a.steps * 1e3
+    step_alg = t.algorithmic_bytes(a.bits, delta)
+    res = {
+        "value": round(4.0 * N * world * a.steps / el / 1e9, 2), "ms_per_step": round(step_ms, 4),
+        "desc": W["desc"], "split": split, "inflight": len(slots), "rotation": W["rot"],
+        "elements_per_gpu": N, "segments_per_gpu": T, "kept_per_gpu": K,
+        "step_roofline": {"alg_bytes_per_step": step_alg, "achieved_GBs": round(step_alg / (step_ms * 1e-3) / 1e9, 1),
+                          "frac": round(step_alg / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+        "sample_fallbacks": W.get("fallbacks", 0),
+        "graph": W["graph_error"] or (graphs is not None and f"{W['gk']} step(s) per graph launch"),
+        "rank_ms_per_step": rank_spread(rank_el, a.steps),
+    }
+    if not a.full:  # a plain run: the headline figure only
+        return res
     # the same K steps timed again in a few more windows (not part of `value`): the spread a single short window
-    # cannot show (box-to-box and run-to-run variance)
+    # cannot show (machine-to-machine and run-to-run variance)
     rep_ms = sorted(timed_region() / a.steps * 1e3 for _ in range(a.repeat_windows))
 
     # Roofline steps (after the timed region, not part of `value`): per sub-batch, HIP events [1] / [2]
@@ -494,8 +577,6 @@ def time_workload(W, a, dev, world):
     for name, which in {"k_scan": ev_e, "k_decode": ev_d}.items():
         per = [union([(e[1], e[2]) for e in which[i]]) for i in timed_steps]
         stages[name] = sum(per) / len(per)
-    N, K, T = t.n_elements, t.total_k, t.n_segments
-    delta = W["mode"] == "delta"
     vb = 4 if a.bits == 32 else 1
     large_elems = large_elements(pipes[0])
     alg = {  # algorithmic HBM bytes per timed interval
@@ -507,27 +588,17 @@ def time_workload(W, a, dev, world):
         alg = {"k_scan": 4 * N * (2 if delta else 1) + vb * N, "k_decode": 4 * N * (2 if delta else 1) + vb * N + 8 * T}
     dom = max(alg, key=lambda k: stages[k])
     ach = alg[dom] / (stages[dom] * 1e-3) / 1e9
-    step_ms = el / a.steps * 1e3
-    step_alg = t.algorithmic_bytes(a.bits, delta)
     kname = {"k_scan": "k_dense_quant", "k_decode": "k_dense_deq"}[dom] if dense else dom
-    res = {
-        "value": round(4.0 * N * world * a.steps / el / 1e9, 2), "ms_per_step": round(step_ms, 4),
-        "desc": W["desc"], "split": split, "inflight": len(slots), "rotation": W["rot"],
-        "elements_per_gpu": N, "segments_per_gpu": T, "kept_per_gpu": K,
+    res.update({
         "roofline": {"bound": "hbm", "kernel": kname if split == 1 else f"{kname} x{split} concurrent launches (union interval)",
                      "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
                      "alg_bytes_per_launch": int(alg[dom])},
-        "step_roofline": {"alg_bytes_per_step": step_alg, "achieved_GBs": round(step_alg / (step_ms * 1e-3) / 1e9, 1),
-                          "frac": round(step_alg / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
         "stages_ms": {({"k_scan": "k_dense_quant", "k_decode": "k_dense_deq"}[k] if dense else k): round(v, 4)
                       for k, v in stages.items()},
-        "sample_fallbacks": W.get("fallbacks", 0),
-        "graph": W["graph_error"] or (graphs is not None and f"{W['gk']} step(s) per graph launch"),
-        "rank_ms_per_step": rank_spread(rank_el, a.steps),
         "repeat_windows": ({"windows": len(rep_ms), "steps_each": a.steps, "ms_per_step_min": round(rep_ms[0], 4),
                             "ms_per_step_median": round(rep_ms[len(rep_ms) // 2], 4),
                             "ms_per_step_max": round(rep_ms[-1], 4)} if rep_ms else None),
-    }
+    })
     if headline:
         traffic, src = pmc_traffic(dom, W["cfg"], a, split, world)
         res["roofline"]["traffic"] = traffic * split if traffic is not None else None
@@ -766,7 +837,7 @@ def main():
     if a.launch_check:
         sys.exit(launch_check(a, world, rank, local))
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         layout = a.layout or CONFIGS[a.config][0]
         cpu = cpu_baseline(layout if layout != "c5" else "resnet50_tv", a.ratio, a.bits, a.cpu_seconds)
 
@@ -805,10 +876,11 @@ def main():
         if W is None:
             W = setup_workload(cfg, a, dev, rank, headline=cfg == a.config)
             warm_workload(W, a)
-        results[cfg] = time_workload(W, a, dev, world)
+        dump = a.dump_outputs if cfg == a.config and rank == 0 else None  # (rank 0's share of a multi-GPU job)
+        results[cfg] = time_workload(W, a, dev, world, dump_dir=dump)
         release_workload(W)
     head = results.pop(a.config)
-    box = box_probe(torch, dev) if rank == 0 else None
+    box = box_probe(torch, dev) if a.full and rank == 0 else None
 
     if rank == 0:
         d = head["desc"]
@@ -823,11 +895,17 @@ def main():
                        **d, "global_clients": d.get("clients_per_gpu", 0) * world, "ratio": h_ratio, "bits": a.bits,
                        "mode": h_mode, "sub_batches_per_step": head["split"], "inflight_steps": head["inflight"],
                        "parallelism": f"replicas{world}"},
-            "roofline": head["roofline"], "step_roofline": head["step_roofline"], "stages_ms": head["stages_ms"],
-            "stage_timing": head["stage_timing"], "sample_fallbacks": head["sample_fallbacks"],
-            "graph": head["graph"], "rank_ms_per_step": head["rank_ms_per_step"],
-            "repeat_windows": head["repeat_windows"],
+            "step_roofline": head["step_roofline"], "sample_fallbacks": head["sample_fallbacks"],
+            "graph": head["graph"], "rank_ms_per_step": head["rank_ms_per_step"], "full": a.full,
         }
+        if a.dump_outputs:
+            res["dump_outputs"] = a.dump_outputs
+        if not a.full:
+            print(json.dumps(res), flush=True)
+            if world > 1:
+                dist.destroy_process_group()
+            return
+        res.update({f: head[f] for f in ("roofline", "stages_ms", "stage_timing", "repeat_windows")})
         # cpu_baseline and box BEFORE the per-config details, and a compact summary of every config LAST: the driver
         # keeps only the tail of stdout, so every config's number must sit in the line's last ~2 KB
         if cpu is not None:

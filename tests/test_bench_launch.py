@@ -146,3 +146,19 @@ def test_pmc_traffic_only_for_one_gpu(monkeypatch):
     traffic8, src8 = bench.pmc_traffic("k_scan", "C3", a, bench.SPLIT, world=8)
     assert traffic8 is None and src8 is None
     assert traffic1 is not None  # the committed one-GPU summary
+
+
+def test_plain_run_times_the_headline_only(monkeypatch, capsys):
+    """Without --full the run has no extra configs (and --extras is refused); --full brings the default extras back."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.extras, a.steps, a.warmup, a.dump_outputs) == (False, "none", 7, 2, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and a.extras == bench.DEFAULT_EXTRAS and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--extras", "C2"])
+    assert bench.parse().extras == "C2"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--extras", "C2"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    assert "--extras needs --full" in capsys.readouterr().err

@@ -8,7 +8,7 @@ OUT=gpurun_out/ab_${TAG}.txt
 : > "$OUT"
 for r in $(seq 1 "$R"); do
   for v in "$@"; do
-    COALAC_LIB=coala_amd/lib/variants/$v.so timeout -k 10 180 python3 bench.py --config "$CFG" --extras none \
+    COALAC_LIB=coala_amd/lib/variants/$v.so timeout -k 10 180 python3 bench.py --full --config "$CFG" --extras none \
       --no-cpu-baseline --steps 60 --warmup 5 > gpurun_out/ab_${TAG}_last.json 2>/dev/null
     python3 - "$v" "$OUT" <<'PY'
 import json, sys

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for C in "$@"; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/$C" -o run --output-format csv \
-    -- python3 bench.py --config "$C" --extras none --no-cpu-baseline --steps 20 --warmup 3 > "$OUT/${C}_bench.json" 2> "$OUT/${C}.err"
+    -- python3 bench.py --full --config "$C" --extras none --no-cpu-baseline --steps 20 --warmup 3 > "$OUT/${C}_bench.json" 2> "$OUT/${C}.err"
   find "$OUT/$C" -name '*kernel_stats.csv' -exec cp {} "$OUT/${C}_kernel_stats.csv" \;
   if [ -n "$KEEP_TRACE" ]; then find "$OUT/$C" -name '*kernel_trace.csv' -exec cp {} "$OUT/${C}_kernel_trace.csv" \; ; fi
   rm -rf "$OUT/$C"

@@ -11,7 +11,7 @@ TAG=${1:-r03}
 OUT=gpurun_out/prof_${TAG}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="--no-cpu-baseline --extras none"
+B="--full --no-cpu-baseline --extras none"
 S="--config single --graph off"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
   -- python3 bench.py --steps 10 --warmup 3 $B > "$OUT/bench_trace.json" 2> "$OUT/trace.err"

@@ -5,7 +5,7 @@ OUT=gpurun_out/split_${TAG}.txt
 : > "$OUT"
 for r in $(seq 1 "$R"); do
   for s in "$@"; do
-    timeout -k 10 180 python3 bench.py --config "$CFG" --split "$s" --extras none --no-cpu-baseline --steps 60 --warmup 5 \
+    timeout -k 10 180 python3 bench.py --full --config "$CFG" --split "$s" --extras none --no-cpu-baseline --steps 60 --warmup 5 \
       > gpurun_out/split_${TAG}_last.json 2>/dev/null
     python3 -c "
 import json; d=json.loads(open('gpurun_out/split_${TAG}_last.json').read().strip().splitlines()[-1])
