@@ -42,6 +42,9 @@ SIGNATURES = [
     ("coalac_encode_segptr", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P]),
     # decode: plan, idx, vals, mn, scale, ustart, base, out, stream (+ events)
     ("coalac_decode", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # error feedback: plan, in, seg pointers, base, resid, stream / plan, idx, vals, mn, scale, ustart, resid, stream
+    ("coalac_ef_accumulate", _I, [_P, _P, _P, _P, _P, _P]),
+    ("coalac_ef_commit", _I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -53,7 +56,7 @@ SIGNATURES = [
     ("coalac_debug_brackets", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _I]),
 ]
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class CodecError(RuntimeError):
@@ -88,13 +91,16 @@ def load(build_if_missing=True):
                 raise CodecError(f"HIP codec library not found at {path}; run __graft_entry__.build()")
             _build.build()
         lib = ctypes.CDLL(path)
+        # the version first: a library of another ABI (a COALAC_LIB variant, a stale .so where hipcc is absent) may
+        # lack symbols this binding names, and must fail with the version message, not an AttributeError
+        lib.coalac_version.restype, lib.coalac_version.argtypes = _I, []
+        v = lib.coalac_version()
+        if v != ABI_VERSION:
+            raise CodecError(f"libcoalac ABI version {v} != expected {ABI_VERSION} ({path}: rebuild it from this tree)")
         for name, res, args in SIGNATURES:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        v = lib.coalac_version()
-        if v != ABI_VERSION:
-            raise CodecError(f"libcoalac ABI version {v} != expected {ABI_VERSION}")
         _lib = lib
         return lib
 

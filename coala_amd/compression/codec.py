@@ -816,19 +816,38 @@ class UpdateCodec:
         release_decode_pool()
 
     # -- encode -----------------------------------------------------------------------------------
-    def encode(self, state, base=None, device=None):
+    def encode(self, state, base=None, device=None, residual=None):
         """state_dict -> CompressedUpdate. `base` (delta mode): FlatState of w_global (same layout).
         `device`: where to flatten and encode (default: where the state lives if the backend runs there,
-        else the backend's default device — a model trained on the CPU is encoded on the GPU)."""
+        else the backend's default device — a model trained on the CPU is encoded on the GPU).
+        `residual` (delta mode only): this client's error-feedback memory (new_residual), updated in place:
+        the update encoded is (state - base) + residual, and what the payload does not carry of it stays in
+        the residual for the next round. The payload is an ordinary delta-mode one."""
         if device is None:
             device = self._device_for(state.values())
         L, segs, raw = _describe(state)
-        return self._encode(L, segs, raw, base, device, lambda: state)
+        return self._encode(L, segs, raw, base, device, lambda: state, residual=residual)
 
-    def encode_module(self, module, base=None, device=None):
+    def new_residual(self, module_or_state, device=None):
+        """A zeroed error-feedback memory for a model of this layout: fp32[span] (the flat layout of its fp32
+        entries, 4 bytes per parameter) on the encode device."""
+        if isinstance(module_or_state, nn.Module):
+            names, tensors, walk = _module_walk(module_or_state)
+            L = _layout_walk(names, tensors, walk)[0].L
+        else:
+            tensors = list(module_or_state.values())
+            L = _layout(module_or_state)
+        if device is None:
+            device = self._device_for(tensors)
+        if not L.sizes:
+            return torch.zeros(0, dtype=torch.float32, device=device)
+        device = torch.device(device)
+        return torch.zeros(int(self.plan_for(L.sizes_key, device).table.span), dtype=torch.float32, device=device)
+
+    def encode_module(self, module, base=None, device=None, residual=None):
         """module -> CompressedUpdate of its state_dict (what CompressionClientMixin.compression() runs): the
         same result as encode(module.state_dict(), ...), with the state read through a cached walk of the
-        module tree (module_tensors) instead of building the state_dict."""
+        module tree (module_tensors) instead of building the state_dict. residual: as encode()."""
         names, tensors, walk = _module_walk(module)
         if device is None:
             device = self._device_for(tensors)
@@ -837,10 +856,13 @@ class UpdateCodec:
         # the passthrough snapshot is taken after the encode's launches (stream order: the same values), so
         # the GPU starts on the segments one gather launch earlier
         return self._encode(d.L, segs, lambda: _raw_snapshot(d, tensors, gather), base, device,
-                            lambda: OrderedDict(zip(names, tensors)), d.seg_ptrs)
+                            lambda: OrderedDict(zip(names, tensors)), d.seg_ptrs, residual=residual)
 
-    def _encode(self, L, segs, raw, base, device, state_fn, ptrs=None):
+    def _encode(self, L, segs, raw, base, device, state_fn, ptrs=None, residual=None):
         """raw: the RawState, or a function that takes it (called once the encode is enqueued)."""
+        if residual is not None and self.mode != "delta":
+            raise ValueError(f"error feedback (residual=) needs mode 'delta', not {self.mode!r}: the memory holds "
+                             "what earlier updates dropped, which only adds to an update, never to the weights")
         if self.mode == "delta" and base is None:
             raise ValueError("delta mode needs the global-model snapshot (base)")
         entries = L.entries
@@ -860,6 +882,14 @@ class UpdateCodec:
             # set_model runs before pretrain moves the model to its device, client/base.py:138 vs :245)
             base_flat = base.flat_on(device)
         plan = self.plan_for(L.sizes_key, device)
+        if residual is not None:
+            if getattr(plan, "ef_accumulate", None) is None or getattr(plan, "ef_commit", None) is None:
+                raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
+                                   "has no ef_accumulate / ef_commit: error feedback is not available on it")
+            if residual.dtype != torch.float32 or residual.device != device or residual.dim() != 1 or \
+                    residual.numel() != int(plan.table.span):
+                raise ValueError(f"residual: need float32[{int(plan.table.span)}] on {device} (new_residual), got "
+                                 f"{residual.dtype}{list(residual.shape)} on {residual.device}")
         cur = torch.cuda.current_stream(device) if device.type == "cuda" else None  # (looked up once per call)
         ws = self._workspace(plan, cur)
         dev_index = device.index if device.type == "cuda" else -1  # (Tensor.get_device(): -1 on the CPU)
@@ -879,7 +909,16 @@ class UpdateCodec:
                             and not any(p & 15 for p in ptrs))
                 if in_place:
                     self._checked_ptrs[id(plan)] = ptrs
-        if in_place:  # read the parameters where they live: no flattening copy (+8 B/element of traffic)
+        if residual is not None:
+            # error feedback, in stream order: residual = (state - base) + residual; the plain encode of that; then
+            # residual -= what the payload reconstructs, at its kept entries
+            if in_place:
+                plan.ef_accumulate(residual, tensors=segs, base=base_flat, stream=cur, checked=True, ptrs=ptrs)
+            else:
+                plan.ef_accumulate(residual, flat=flatten_state(state_fn(), device=device).flat, base=base_flat)
+            enc = plan.encode(residual, base=None, workspace=ws)
+            plan.ef_commit(enc, residual)
+        elif in_place:  # read the parameters where they live: no flattening copy (+8 B/element of traffic)
             # (dtype and sizes hold by construction: the plan was made from this layout's segments)
             enc = plan.encode_segments(segs, base=base_flat, workspace=ws, checked=True, ptrs=ptrs, launch=cur)
         else:

@@ -280,6 +280,42 @@ class CodecPlan:
         _lib.check(rc, "coalac_encode_segptr")
         return out
 
+    # -- error feedback ---------------------------------------------------------------------------
+    def ef_accumulate(self, resid, flat=None, tensors=None, base=None, stream=None, checked=False, ptrs=None):
+        """resid = (x - base) + resid over every segment (coalac_ef_accumulate; fp32 subtract then add, base None:
+        x + resid), x read from `flat` (fp32[span]) or from `tensors` (one per segment, as encode_segments reads
+        them) — exactly one of the two. The padding between segments is not written. Asynchronous on `stream`.
+        An error-feedback round is ef_accumulate, encode(resid), ef_commit, all on one stream."""
+        if (flat is None) == (tensors is None):
+            raise ValueError("ef_accumulate: give exactly one of flat and tensors")
+        self._check_flat(resid, "residual")
+        self._check_flat(base, "base")
+        launch = torch.cuda.current_stream(self.device) if stream is None else stream
+        if tensors is not None:
+            seg, x = _ptr(self.segment_pointers(tensors, checked=checked, ptrs=ptrs, stream=launch)), _ptr(None)
+        else:
+            self._check_flat(flat, "input")
+            seg, x = _ptr(None), _ptr(flat)
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_ef_accumulate(self._h, x, seg, _ptr(base), _ptr(resid),
+                                                ctypes.c_void_p(launch.cuda_stream))
+        _lib.check(rc, "coalac_ef_accumulate")
+        return resid
+
+    def ef_commit(self, enc, resid, stream=None):
+        """resid[pos] -= what decode(enc) reconstructs there, at every kept entry of enc (coalac_ef_commit; +0.0
+        where the difference is not finite); the other positions are left as they are. enc: the Encoded of
+        encode(resid) on the same stream. A sparse plan needs enc.ustart (the encode writes it)."""
+        ust = self._check_encoded(enc)
+        if not self.dense and (enc.ustart is None or enc.idx.numel() < self.total_k):
+            raise ValueError("ef_commit: a sparse plan needs the encode's idx and per-unit starts (ustart)")
+        self._check_flat(resid, "residual")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_ef_commit(self._h, _idx_ptr(enc.idx), _ptr(enc.vals), _ptr(enc.mn), _ptr(enc.scale),
+                                            ust, _ptr(resid), _stream_handle(stream))
+        _lib.check(rc, "coalac_ef_commit")
+        return resid
+
     def unit_starts(self, idx, stream=None):
         """The per-unit starts (wire v2) of this plan's idx list, computed on the device for a payload that carries
         none (a version-1 blob, or an Encoded built without them): for unit j of segment s, the number of the

@@ -26,6 +26,9 @@ Behaviour:
     leaves a CompressedUpdate carrier in self.model, which construct_upload_request deep-copies and
     pickles into UploadContent.data (base.py:363). post_upload() puts the trained module back so the
     next round's set_model (base.py:197-201) works.
+  * error feedback (opt-in, `codec_error_feedback = True`, delta mode): compression() adds the client's residual —
+    what its earlier uploads dropped — to the update before the top-k and keeps what this upload drops
+    (reset_error_feedback() zeroes it). The upload is an ordinary delta-mode carrier; the server is unchanged.
   * calculate_model_size(): reports the real payload size for a carrier (base.py:155, 474-487).
   * server decompression(model): CompressedUpdate -> a NEW nn.Module (never aliases self.model, which
     aggregation overwrites, base.py:571) built on the pre-aggregation global model (delta mode: w_global
@@ -53,7 +56,7 @@ import threading
 
 from torch import nn
 
-from .codec import CompressedUpdate, UpdateCodec
+from .codec import CompressedUpdate, UpdateCodec, _layout_walk, _module_walk
 from .download import CompressedModel, compress_model
 
 DATA_TYPE_FEATURE = 2  # coala/pb/common.proto: DataType.DATA_TYPE_FEATURE (protos/coala/pb/common.proto:26)
@@ -110,6 +113,30 @@ class CompressionClientMixin(_CodecOwner):
     codec_feature_ratio = None    # their top-k ratio (None: codec_ratio)
     codec_feature_bits = None     # their code width (None: codec_bits)
 
+    # error feedback for the top-k upload (delta mode): what an upload drops stays in a per-client residual on the
+    # encode device (4 bytes per fp32 parameter per client) and is added to the next round's update, so nothing is
+    # lost, only delayed (EF-SGD). Off by default: uploads are then exactly what they were.
+    codec_error_feedback = False
+
+    def reset_error_feedback(self):
+        """Zero this client's residual (e.g. when it joins a new task with the same model)."""
+        held = self.__dict__.get("_codec_residual")
+        if held is not None:
+            held[1].zero_()
+
+    def _error_feedback_residual(self, codec, model):
+        """The client's residual for `model`, created zeroed on first use and again whenever the model's layout or
+        device changes."""
+        if codec.mode != "delta":
+            raise ValueError("codec_error_feedback needs codec_mode 'delta': the residual holds the part of earlier "
+                             f"updates that was not uploaded, and mode {codec.mode!r} uploads weights, not updates")
+        names, tensors, walk = _module_walk(model)
+        key = (_layout_walk(names, tensors, walk)[0].L.sizes_key, codec._device_for(tensors))
+        held = self.__dict__.get("_codec_residual")
+        if held is None or held[0] != key:
+            held = self.__dict__["_codec_residual"] = (key, codec.new_residual(model))
+        return held[1]
+
     def _feature_codec(self):
         c = self.__dict__.get("_feature_update_codec")
         if c is None:
@@ -157,7 +184,10 @@ class CompressionClientMixin(_CodecOwner):
             return
         codec = self._codec()
         base = getattr(self, "_codec_base", None) if codec.mode == "delta" else None
-        update = codec.encode_module(model, base=base)
+        if self.codec_error_feedback:
+            update = codec.encode_module(model, base=base, residual=self._error_feedback_residual(codec, model))
+        else:
+            update = codec.encode_module(model, base=base)
         self._codec_trained_model = model
         self.model = update
         # §8(f) 3: the compression ratio next to TRAIN_UPLOAD_SIZE (client/base.py:155); an unknown

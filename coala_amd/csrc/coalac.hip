@@ -43,6 +43,8 @@
 //   holding the unkept x (base + 0), each client's kept values written in and read back in client order.
 //   Dense plans (every segment keeps all its elements, ratio 1): k_dense_minmax -> k_dense_seg -> k_dense_quant
 //   encode, k_dense_deq decode — the indices implied, never materialised.
+//   Error feedback (client side): k_ef_accumulate (r = (x - base) + r, one stream) before an encode of
+//   r, k_ef_commit / k_ef_commit_dense (r -= what the decoder will reconstruct, at the kept entries) after it.
 //
 // Numerics: built with -ffp-contract=off; fp32 sub/div/mul/add are separate IEEE ops, rintf is
 // round-half-even — the same op sequence as the oracle, so decoded values are bit-identical.
@@ -2181,12 +2183,13 @@ __global__ __launch_bounds__(NT) void k_select(Params P) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_emit: EMIT_UPW consecutive large units per wave — each unit's candidate list is already in index
-// order: keep key > T and the ties whose segment-wide tie rank is < rt, compact with ballots, write idx +
-// code. No LDS. A unit holds ~1.5 % of its 4096 elements as candidates (about one record per lane), so
-// one unit per wave was a chain of dependent loads (count -> unit/segment metadata -> records) per 64
-// records: here lane g loads unit g's metadata (two dependent rounds for all units at once) and every
-// unit's first 64 records are in flight before the first one is classified.
+// k_emit: a block takes a tile of WAVES * UPW consecutive large units and its waves interleave them (wave w takes
+// units w, w + WAVES, ...: emit_units' stride) — each unit's candidate list is already in index order: keep
+// key > T and the ties whose segment-wide tie rank is < rt, compact with ballots, write idx + code. No LDS. A unit
+// holds ~1.5 % of its 4096 elements as candidates (about one record per lane), so one unit per wave was a chain of
+// dependent loads (count -> unit/segment metadata -> records) per 64 records: here lane g loads the metadata of the
+// wave's g-th unit (two dependent rounds for all its units at once) and every unit's first 64 records are in flight
+// before the first one is classified.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t EMIT_UPW = 4u;  // large units per k_emit wave in batches (round 6, with the interleaved tile: 4 vs 8
                                    // C3 0.586-0.595 vs 0.608-0.639 ms, C2 0.271 vs 0.275-0.278, C3_signs 1.427-1.436 vs
@@ -2933,16 +2936,12 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
   if (P.ustart_out != nullptr && lane == 0) P.ustart_out[u] = U.start;
 }
 
-template <bool RAW, bool HASBASE, bool XCD>
-__global__ __launch_bounds__(BLOCK) void k_dense_deq(Params P) {
-  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
-  if (u >= P.n_units) return;
-  const UnitDev U = P.units[u];
-  const uint32_t lane = lane_id();
-  const float mn = RAW ? 0.0f : P.cmn[U.seg], scale = RAW ? 0.0f : P.cscale[U.seg];
+// the decoded values of a dense plan's unit (its codes sit at the positions themselves): lane l's float4 of row it
+// in d[it]; positions past the unit's end hold mn (code 0) or 0.0f (raw) and are never stored
+template <bool RAW>
+DEV void dense_unit_values(const Params& P, const UnitDev& U, float mn, float scale, uint32_t lane, float4 (&d)[UNIT_IT]) {
   const uint64_t o = U.out_off + U.start;
   const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;
-  float4 d[UNIT_IT];
   if (RAW) {
     const float* src = static_cast<const float*>(P.cvals) + o;
     const __amdgpu_buffer_rsrc_t r = unit_rsrc(src, U.len);
@@ -2980,6 +2979,17 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq(Params P) {
       d[it] = make_float4(dequantize((uint8_t)(w[it] & 0xFFu), mn, scale), dequantize((uint8_t)((w[it] >> 8) & 0xFFu), mn, scale),
                           dequantize((uint8_t)((w[it] >> 16) & 0xFFu), mn, scale), dequantize((uint8_t)(w[it] >> 24), mn, scale));
   }
+}
+
+template <bool RAW, bool HASBASE, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_deq(Params P) {
+  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id();
+  const float mn = RAW ? 0.0f : P.cmn[U.seg], scale = RAW ? 0.0f : P.cscale[U.seg];
+  float4 d[UNIT_IT];
+  dense_unit_values<RAW>(P, U, mn, scale, lane, d);
   const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
   const __amdgpu_buffer_rsrc_t rb = unit_rsrc(HASBASE ? P.base + U.off : P.out + U.off, U.len);
 #pragma unroll
@@ -2993,6 +3003,118 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq(Params P) {
       unit_store_x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
     else
       unit_store_x1x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// error feedback (client side): the residual memory of a top-k upload, DESIGN.md §11
+//   k_ef_accumulate  r = (x - base) + r over every unit of the plan (fp32 subtract, then fp32 add): the encoder then
+//                    runs on r as a plain input
+//   k_ef_commit      r[pos] = r[pos] - xhat at every kept entry (xhat: code_value, the decoder's own arithmetic), +0.0f
+//                    where that is not finite; positions not kept still hold the accumulated value, which IS the residual
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t EF_ROWS = 4u;   // rows (float4 per lane) of each operand in flight per k_ef_accumulate wave: 12 b128
+                                   // loads per lane with a base, and few enough registers for 8 waves per SIMD
+constexpr int EF_STORE_AUX = 0;    // cache policy of the residual's stores (0 plain, 2 non-temporal): the encode reads
+                                   // them next (A/B in DESIGN.md §11)
+
+template <bool HASBASE>
+__global__ __launch_bounds__(BLOCK) void k_ef_accumulate(Params P) {
+  static_assert(UNIT_IT % EF_ROWS == 0, "accumulate batch geometry");
+  const uint32_t u = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id(), len = U.len;
+  const float* x = P.inptr != nullptr ? P.inptr[U.seg] + U.start : P.in + U.off;
+  // range-checked operands: a load past the unit's end gives 0, a store past it is dropped (the padding between
+  // segments is never written)
+  const __amdgpu_buffer_rsrc_t rx = unit_rsrc(x, len);
+  const __amdgpu_buffer_rsrc_t rb = unit_rsrc(HASBASE ? P.base + U.off : x, len);
+  const __amdgpu_buffer_rsrc_t rr = unit_rsrc(P.out + U.off, len);
+  const uint32_t rows = (len + 255u) >> 8;  // rows that hold elements (wave-uniform)
+  for (uint32_t i0 = 0; i0 < rows; i0 += EF_ROWS) {
+    float4 d[EF_ROWS], r[EF_ROWS];
+#pragma unroll
+    for (uint32_t it = 0; it < EF_ROWS; ++it) {
+      const uint32_t b = ((i0 + it) * 64 + lane) * 16;
+      d[it] = unit_load_x4<HASBASE>(rx, rb, b);
+      r[it] = unit_load_x4<false>(rr, rr, b);
+    }
+#pragma unroll
+    for (uint32_t it = 0; it < EF_ROWS; ++it) {
+      const uint32_t b = ((i0 + it) * 64 + lane) * 16;
+      const float4 a = make_float4(d[it].x + r[it].x, d[it].y + r[it].y, d[it].z + r[it].z, d[it].w + r[it].w);
+      if ((len & 3u) == 0)
+        unit_store_x4<EF_STORE_AUX>(rr, b, a);
+      else
+        unit_store_x1x4<EF_STORE_AUX>(rr, b, a);
+    }
+  }
+}
+
+// a - xhat, or +0.0f when that is NaN or +-Inf (a diverged element must not stay in the memory)
+DEV float ef_residual(float a, float xhat) {
+  const float v = a - xhat;
+  return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u ? 0.0f : v;
+}
+
+// one wave per unit; the unit's entry range from the per-unit starts, clamped as k_decode_lds clamps it; a lane takes
+// one entry at a time (two rounds of 64 in flight). An entry whose position lies outside the unit (never from this
+// library's encoder) is dropped.
+template <bool RAW>
+__global__ __launch_bounds__(BLOCK) void k_ef_commit(Params P) {
+  const uint32_t u = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const uint32_t lane = lane_id();
+  const UnitDev U = P.units[u];
+  uint32_t lo = P.ustart[u];
+  uint32_t hi = P.ustart[min(u + 1, P.n_units - 1)];
+  const float mn = RAW ? 0.0f : P.cmn[U.seg], sc = RAW ? 0.0f : P.cscale[U.seg];
+  lo = min(lo, U.k);
+  hi = max(lo, min(min(U.last ? U.k : hi, U.k), lo + U.len));
+  float* r = P.out + U.off;
+  for (uint32_t e0 = lo; e0 < hi; e0 += 128) {
+    uint32_t pos[2], q[2];
+    float a[2];
+    bool ok[2];
+#pragma unroll
+    for (uint32_t c = 0; c < 2; ++c) {
+      const uint32_t ei = e0 + c * 64 + lane;
+      const uint64_t e = U.out_off + min(ei, hi - 1);
+      pos[c] = (uint32_t)P.cidx[e] - U.start;
+      q[c] = load_code<RAW>(P, e);
+      ok[c] = ei < hi && pos[c] < U.len;
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < 2; ++c)
+      if (ok[c]) a[c] = r[pos[c]];
+#pragma unroll
+    for (uint32_t c = 0; c < 2; ++c)
+      if (ok[c]) r[pos[c]] = ef_residual(a[c], code_value<RAW>(q[c], mn, sc));
+  }
+}
+
+// a dense plan: every position is a kept entry, taken positionally
+template <bool RAW>
+__global__ __launch_bounds__(BLOCK) void k_ef_commit_dense(Params P) {
+  const uint32_t u = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id();
+  const float mn = RAW ? 0.0f : P.cmn[U.seg], scale = RAW ? 0.0f : P.cscale[U.seg];
+  float4 d[UNIT_IT];
+  dense_unit_values<RAW>(P, U, mn, scale, lane, d);
+  const __amdgpu_buffer_rsrc_t rr = unit_rsrc(P.out + U.off, U.len);
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    const uint32_t b = (it * 64 + lane) * 16;
+    const float4 a = unit_load_x4<false>(rr, rr, b);
+    const float4 v = make_float4(ef_residual(a.x, d[it].x), ef_residual(a.y, d[it].y), ef_residual(a.z, d[it].z),
+                                 ef_residual(a.w, d[it].w));
+    if ((U.len & 3u) == 0)
+      unit_store_x4<EF_STORE_AUX>(rr, b, v);
+    else
+      unit_store_x1x4<EF_STORE_AUX>(rr, b, v);
   }
 }
 
@@ -3688,6 +3810,71 @@ int coalac_decode_ev(coalac_plan_t plan, const int32_t* d_idx, const void* d_val
 int coalac_decode(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
                   const float* d_scale, const uint32_t* d_ustart, const float* d_base, float* d_out, void* stream) {
   return coalac_decode_ev(plan, d_idx, d_vals, d_mn, d_scale, d_ustart, d_base, d_out, stream, nullptr);
+}
+
+int coalac_ef_accumulate(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                         float* d_resid, void* stream) {
+  // (the argument checks come before any use of the plan)
+  if (!plan) return fail(COALAC_EINVAL, "coalac_ef_accumulate: plan is NULL");
+  if ((d_in != nullptr) == (d_seg_in != nullptr))
+    return fail(COALAC_EINVAL, "coalac_ef_accumulate: exactly one of d_in and d_seg_in must be given");
+  if (!d_resid) return fail(COALAC_EINVAL, "coalac_ef_accumulate: residual pointer is NULL");
+  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_base) | reinterpret_cast<uintptr_t>(d_resid)) & 15)
+    return fail(COALAC_EINVAL, "coalac_ef_accumulate: input/base/residual must be 16-byte aligned");
+  if (plan->n_units == 0) return COALAC_OK;
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P{};
+  fill_meta(P, plan);
+  P.in = d_in;
+  P.inptr = d_seg_in;
+  P.base = d_base;
+  P.out = d_resid;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 g((plan->n_units + WAVES - 1) / WAVES);
+  if (d_base)
+    hipLaunchKernelGGL((k_ef_accumulate<true>), g, dim3(BLOCK), 0, st, P);
+  else
+    hipLaunchKernelGGL((k_ef_accumulate<false>), g, dim3(BLOCK), 0, st, P);
+  HIP_CHECK(hipGetLastError());
+  return COALAC_OK;
+}
+
+int coalac_ef_commit(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
+                     const float* d_scale, const uint32_t* d_ustart, float* d_resid, void* stream) {
+  if (!plan) return fail(COALAC_EINVAL, "coalac_ef_commit: plan is NULL");
+  if (plan->n_units == 0 || plan->total_k == 0) return COALAC_OK;
+  if (!d_resid) return fail(COALAC_EINVAL, "coalac_ef_commit: residual pointer is NULL");
+  if (!(plan->dense || (d_idx && d_ustart)) || !d_vals)
+    return fail(COALAC_EINVAL, "coalac_ef_commit: idx/vals/ustart pointers are NULL (a sparse plan needs the per-unit "
+                "starts the encode wrote)");
+  if (plan->bits != 32 && (!d_mn || !d_scale)) return fail(COALAC_EINVAL, "coalac_ef_commit: mn/scale pointers are NULL");
+  if (reinterpret_cast<uintptr_t>(d_resid) & 15)
+    return fail(COALAC_EINVAL, "coalac_ef_commit: residual must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_ef_commit: ustart must be 4-byte aligned");
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P{};
+  fill_meta(P, plan);
+  P.cidx = d_idx;
+  P.cvals = d_vals;
+  P.cmn = d_mn;
+  P.cscale = d_scale;
+  P.ustart = d_ustart;
+  P.out = d_resid;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 g((plan->n_units + WAVES - 1) / WAVES);
+  const bool raw = plan->bits == 32;
+  if (plan->dense && raw)
+    hipLaunchKernelGGL((k_ef_commit_dense<true>), g, dim3(BLOCK), 0, st, P);
+  else if (plan->dense)
+    hipLaunchKernelGGL((k_ef_commit_dense<false>), g, dim3(BLOCK), 0, st, P);
+  else if (raw)
+    hipLaunchKernelGGL((k_ef_commit<true>), g, dim3(BLOCK), 0, st, P);
+  else
+    hipLaunchKernelGGL((k_ef_commit<false>), g, dim3(BLOCK), 0, st, P);
+  HIP_CHECK(hipGetLastError());
+  return COALAC_OK;
 }
 
 int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, const void* d_vals,

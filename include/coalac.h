@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define COALAC_ABI_VERSION 5
+#define COALAC_ABI_VERSION 6
 
 enum {
   COALAC_OK = 0,
@@ -57,7 +57,9 @@ enum {
  * decode and aggregate: wire v2. ABI 5 makes them required by the sparse decode and the aggregate — a host that
  * receives a version-1 payload computes them (coala_amd/compression/plan.py) — and drops the decode workspace,
  * the k_bounds / k_fill / k_scatter kernels and the staged (_sched) entry points; plans whose every segment keeps
- * all its elements run the dense codec, with the indices implied.) */
+ * all its elements run the dense codec, with the indices implied. ABI 6 adds the error-feedback pair
+ * coalac_ef_accumulate / coalac_ef_commit — a client-side residual memory around an unchanged encode; no existing
+ * entry point changes.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -119,6 +121,33 @@ int coalac_encode_segptr(coalac_plan_t plan, const float* const* d_seg_in, const
  * positionally (d_idx / d_ustart are not read). */
 int coalac_decode(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
                   const float* d_scale, const uint32_t* d_ustart, const float* d_base, float* d_out, void* stream);
+
+/* Error feedback for a top-k upload (EF-SGD / "sparsified SGD with memory"): what an encode drops is kept in a
+ * per-client residual d_resid (fp32[span], the plan's flat input layout, 16-byte aligned, zero at the start) and added
+ * to the next round's update. One round, all on one stream:
+ *
+ *   coalac_ef_accumulate(plan, d_in | d_seg_in, d_base, d_resid, stream)   r[i] = (x[i] - base[i]) + r[i]
+ *   coalac_encode(plan, d_resid, NULL, ...same stream...)                  the payload of `r` as a plain input
+ *   coalac_ef_commit(plan, idx, vals, mn, scale, ustart, d_resid, stream)  r[pos] = r[pos] - xhat at every kept entry
+ *
+ * accumulate: fp32 subtract, then fp32 add (d_base NULL: r[i] = x[i] + r[i]), for every element of every segment;
+ * the padding between segments is not written. Exactly one of d_in (flat, indexed by in_off) and d_seg_in (a DEVICE
+ * array of per-segment pointers, as coalac_encode_segptr takes) is non-NULL; both or neither is COALAC_EINVAL (checked
+ * before the plan is used).
+ * commit: xhat is what coalac_decode writes for the entry — mn + float(q) * scale, fp32 multiply then fp32 add, or the
+ * stored fp32 value (bits 32) — so the residual is exactly what the server did not reconstruct; a result that is NaN
+ * or +-Inf is stored as +0.0f. Positions that were not kept are left as they are: they hold the accumulated value,
+ * which is their residual. A sparse plan needs d_idx and d_ustart (NULL: COALAC_EINVAL); a dense plan takes every
+ * position as a kept entry and reads neither.
+ * Both are one asynchronous launch: no allocation, no workspace, no host synchronisation; they follow the plan's unit
+ * table, so batched (`clients` copies) and explicit-row plans work alike. Stream order suffices between the three
+ * calls: coalac_encode may fork small segments to the plan's side stream, but it makes `stream` wait for that
+ * stream's join event before it returns (launch_encode), so work enqueued on `stream` afterwards sees every output of
+ * the encode. The payload is an ordinary one: with d_base given to accumulate, the server decodes it as delta mode. */
+int coalac_ef_accumulate(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                         float* d_resid, void* stream);
+int coalac_ef_commit(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
+                     const float* d_scale, const uint32_t* d_ustart, float* d_resid, void* stream);
 
 /* Profiling variants: identical work, plus hipEventRecord(events[i], stream) between kernels.
  * encode: [0] before k_sample, [1] after k_sample, [2] after k_scan, [3] after the select kernels
