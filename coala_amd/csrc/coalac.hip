@@ -172,8 +172,10 @@ struct Params {
   uint4* uemit;  // per large unit, from k_select: {T*, tie budget | raw-path flag << 31, mn bits, scale bits}
   uint32_t* cval;  // candidate records, ccap slots per large unit, in index order: the value bits ...
   uint16_t* cpos;  // ... and the position inside the unit (the emit reads both; every select sweep the values only)
-  uint32_t ccap;  // record slots per large unit (< UNIT: a unit that finds more candidates overflows and its
-                  // segment is selected and emitted from the raw data instead)
+  uint32_t ccap;  // record slots per large unit, in [STAGE_CAP, UNIT] (below UNIT a unit that finds more candidates
+                  // overflows and its segment is selected and emitted from the raw data instead; coalac_plan_create's
+                  // UNIT * (2 rmax + 0.05) + 256 reaches UNIT from a largest ratio of ~0.44 on, and is UNIT for every
+                  // rmax >= 0.475: every element can be a record and no unit overflows)
   // parallel select (groups of GU units of one large segment)
   const uint4* groups;     // {large-segment index, first large unit, units, segment}
   const uint4* gseg;       // per group, its segment: {first large unit, units, k, first group}

@@ -64,7 +64,9 @@ enum {
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
  *   n      : element count, 0 <= n < 2^31
- *   k      : kept elements, 0 if n == 0 else 1 <= k <= n (host computes max(1, min(n, ceil(n*ratio))))
+ *   k      : kept elements, 0 if n == 0 else 1 <= k <= n (host computes max(1, min(n, ceil(n*ratio)))). Any
+ *            1 <= k <= n is accepted per segment, independently of the other segments' (k = 1, n - 1 and n of a
+ *            large segment inside a sparse plan included), and tested so: tests/test_gpu_high_ratio.py.
  *   out_off: start of this segment's k entries in the idx / vals arrays                              */
 typedef struct coalac_seg {
   uint64_t in_off;

@@ -164,19 +164,24 @@ def ccap_for(ratios):
     return max(512, min(4096, c))
 
 
-def takes_raw_path(x, k, tlo, thi, ccap):
+def takes_raw_path(x, k, tlo, thi, ccap, generic=False):
     """Whether the segment falls back to the raw-data path with this bracket: a unit with more candidate records than
     its ccap slots (candidates: keys >= T_lo, or in tie mode the keys above K), or a bracket that misses the k-th key
-    (segment_pick / select_fallback)."""
+    (segment_pick / select_fallback: the records hold it when sa <= k <= sc, sa of them above T_hi; sa == k goes
+    through the generic select, rank 0 below T_hi). In tie mode a k-th key equal to K is resolved from the counted
+    K-keys (sc < k <= sc + sz) — unless the generic select is forced (generic: COALAC_FLAG_GENERIC_SELECT; a segment of
+    more than 2048 units is forced too), where segment_pick skips that shortcut and select_fallback, finding k > sc,
+    re-reads the raw data."""
     keys = (x.view(np.uint32) & np.uint32(KEY_MAX)).astype(np.int64)
+    generic = generic or (x.size + 4095) // 4096 > 2048
     if tlo == 0 or tlo & TIE_FLAG:
         K = tlo & KEY_MAX
         cand = keys > K
         sc, sz, sa = int(cand.sum()), int((keys == K).sum()), int((keys > thi).sum())
-        ok = (sc < k <= sc + sz) or (sa < k <= sc)
+        ok = (not generic and sc < k <= sc + sz) or (sa <= k <= sc)
     else:
         cand = keys >= tlo
         sa, sc = int((keys > thi).sum()), int(cand.sum())
-        ok = sa < k <= sc
+        ok = sa <= k <= sc
     per_unit = np.add.reduceat(cand.astype(np.int64), np.arange(0, x.size, 4096))
     return (not ok) or bool((per_unit > ccap).any())
