@@ -21,12 +21,15 @@
 //   streaming pass has no block barriers. Segments of <= 1024 elements ("small"; COALAC_SMALL_MAX raises the
 //   limit up to 4096) are encoded whole by one block in LDS.
 //
-//   Encode kernels, in stream order:
-//     k_presel  the samplers (one block per large segment: stratified sample -> [T_lo, T_hi]) and the small
-//               segments side by side (batches; latency-bound plans run k_sample alone and the small
-//               segments in k_scan's first blocks)
+//   Encode kernels, in stream order (launch_encode picks by plan class; "latency-bound" = at most
+//   LATENCY_PLAN_UNITS large units, "batch" = more, "fork class" = small segments beside >= 16384 large units):
+//     k_presel  batch plans: the samplers (one block per large segment: stratified sample -> [T_lo, T_hi]) and
+//               the small segments (one block each) side by side
+//     k_sample  latency-bound plans, the fork class and plans without small segments: the samplers alone
+//     k_small   the fork class: the small segments on the plan's side stream, beside k_sample / k_scan
 //     k_scan    one wave per large unit (128-thread blocks in batches): single HBM read, classify A / B,
-//               candidate records in index order (u16 position + u32 value bits, 6 B each)
+//               candidate records in index order (u16 position + u32 value bits, 6 B each); in latency-bound
+//               plans its first blocks encode the small segments (the WITH_SMALL instantiation)
 //     k_ghist   one block per 32-unit group: band histogram of the group's B records
 //     k_gwin    one block per group: sum the segment's group histograms -> key window of the k-th key
 //               (every group block of the segment, redundantly); per-unit counts above the window + the
@@ -34,7 +37,7 @@
 //     k_select  one block per large segment: exact k-th key + tie quota from the window lists (generic
 //               multi-pass select / exact re-select on a bracket miss), per-unit output offsets (= the
 //               payload's per-unit starts, wire v2), min / max -> scale, per-unit emit parameters
-//     k_emit    one wave per 8 large units (1 in latency-bound plans, one load round): kept records ->
+//     k_emit    one wave per EMIT_UPW large units (1 in latency-bound plans, one load round): kept records ->
 //               ascending idx + codes
 //   Decode: k_decode_lds — every output line written once, the unit's kept values placed through a per-wave
 //   LDS tile; entry ranges from the payload's per-unit starts (wire v2; a host that received a v1 blob computes
@@ -82,8 +85,7 @@ constexpr uint32_t SMALL_MAX_LATENCY = 1024;  // ... in latency-bound plans (<= 
                                               // 4096: 14 us, alone on a CU) and the slowest small segment set
                                               // the length of k_presel; bigger segments take the sampled path
 constexpr uint32_t LATENCY_PLAN_UNITS = 8192;  // ~1.3 ResNet-50 updates
-constexpr uint32_t SAMPLE_KEYS = 8192u;
-constexpr uint32_t SAMPLE_MAX = SAMPLE_KEYS;  // sampled keys per large segment
+constexpr uint32_t SAMPLE_MAX = 8192u;  // sampled keys per large segment
 constexpr int SEL_NT = 256;               // threads of a k_select block in batches (4 waves: one per SIMD, so
                                           // a block finds room beside a streaming kernel's waves)
 constexpr int GWIN_NT_LAT = 512;  // k_gwin block in latency-bound plans (256 or 512: one or two histogram bins per thread)
@@ -103,9 +105,8 @@ constexpr int SAMPLE_NT_LAT = 256;  // latency-bound plans' k_sample block size 
 constexpr int LOAD_AUX = 2;   // cache policy of the streaming buffer loads (k_scan, the quantise stream): non-temporal
 constexpr int STORE_AUX = 2;  // cache policy of the streaming buffer stores (batch k_decode_lds, k_dense_deq): non-temporal
 constexpr uint32_t STAGE_CAP = 512;       // candidate records staged in LDS per k_scan wave
-constexpr int GU_UNITS = 32;
 constexpr int GSWEEP = 4;  // units per record-load batch of a balanced group sweep (batch plans)
-constexpr uint32_t GU = GU_UNITS;               // units per select group (k_ghist / k_gwin block)
+constexpr uint32_t GU = 32;               // units per select group (k_ghist / k_gwin block)
 constexpr uint32_t HB2 = 512;             // bins of the per-group band histograms
 constexpr uint32_t GCAP = 256;            // in-window entries a group may hand to k_select
 constexpr uint32_t KEY_MAX = 0x7FFFFFFFu;
@@ -1206,10 +1207,10 @@ __global__ __launch_bounds__(NT) void k_sample(Params P) {
   sample_segment<DELTA, NT>(P, blockIdx.x, hist, sh);
 }
 
-// k_presel: the samplers (blocks [0, n_large)) and the small segments (blocks after them) as one launch —
-// both latency-bound, they run side by side ahead of k_scan, which then streams large units only (small
-// segments inside k_scan held its first blocks and a 25 KB LDS arena: C2 as 2 sub-batches streamed at
-// ~2.3 TB/s)
+// k_presel (batch plans below the fork class): the samplers (blocks [0, n_large)) and the small segments (blocks
+// after them) as one launch — both latency-bound, they run side by side ahead of k_scan, which then streams large
+// units only (small segments inside a batch's k_scan held its first blocks and a 25 KB LDS arena: C2 as 2
+// sub-batches streamed at ~2.3 TB/s). Latency-bound plans launch k_sample and k_scan<WITH_SMALL> instead.
 template <bool DELTA, bool RAW>
 __global__ __launch_bounds__(BLOCK) void k_presel(Params P) {
   __shared__ __attribute__((aligned(16))) uint8_t arena[(SMALL_MAX + HIST_BINS + 64) * 4];
@@ -1222,7 +1223,8 @@ __global__ __launch_bounds__(BLOCK) void k_presel(Params P) {
 }
 
 // k_scan: streams the large units, one wave each. (WITH_SMALL: blocks [0, scan_small) first encode the
-// small segments — no longer launched: k_presel runs them beside the samplers.)
+// small segments — the latency-bound plans' instantiation; batch plans launch the one without, their small
+// segments in k_presel beside the samplers or, in the fork class, in k_small on the side stream.)
 // (WPE / NB: launch-bound blocks per CU and load batches; the latency-bound plans' instantiation, the one
 // WITH_SMALL, takes its own — nothing streams beside it)
 template <bool DELTA, bool RAW, bool WITH_SMALL, int WPE = SCAN_WPE, int NB = SCAN_NB, int NTS = BLOCK,
@@ -2200,7 +2202,6 @@ constexpr uint32_t EMIT_UPW = 4u;  // large units per k_emit wave in batches (ro
 // so fewer per wave shortens the launch (one ResNet-50 update: 8 per wave 13.1 us, 2 per wave 6.0, 1 per
 // wave 5.1)
 constexpr uint32_t EMIT_UPW_LAT = 1u;
-constexpr uint32_t EMIT_UPW_LATENCY = EMIT_UPW_LAT;
 
 // the raw-data emit of one large unit (its segment took the raw-data path): re-read the unit, keep key > T
 // and the ties whose segment-wide rank (eqp + ties before them) is < rt, in index order
@@ -3160,89 +3161,138 @@ int fail(int code, const char* fmt, ...) {
   } while (0)
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+constexpr uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
-struct WsLayout {
-  size_t status;
-  size_t tstar, rtie;
-  size_t tlo, thi, cntA, cntC, cntZ, tsgn, gtC, eqC, eqpre, outoff, uemit;
-  size_t cval, cpos, stamps, ghist, gcnt, glist, gmm, sstate, shhi;
-  size_t umm;  // dense plans: per-unit min / max
-  size_t total;
+// Hands out typed, 256-byte-aligned sub-ranges of one allocation, in call order. With a null base it only measures
+// (every pointer comes out null, `off` ends at the bytes needed), so one walk over a buffer's arrays gives both its
+// size at plan creation and its pointers at a call.
+struct Carver {
+  uint8_t* base;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off = align_up(off + sizeof(T) * count, 256);
+    return p;
+  }
 };
 
-// a dense plan's encode workspace: the per-unit min / max only
-WsLayout ws_layout_dense(size_t U) {
-  WsLayout L{};
-  L.umm = 0;
-  L.total = std::max<size_t>(align_up(8 * U, 256), 256);
-  return L;
+// The encode workspace, listed once: sets P's workspace pointers inside `ws` (null: measures only) from the counts
+// already in P, and returns the bytes the plan needs. A kernel that gets a new array gets it here, and nowhere else.
+size_t carve_workspace(Params& P, bool dense, void* ws) {
+  Carver c{static_cast<uint8_t*>(ws)};
+  const size_t S = P.nseg, LU = P.n_lunits, NG = P.n_groups, NL = P.n_large, CC = P.ccap;
+  if (dense) {  // a dense plan's encode workspace: the per-unit min / max only
+    P.umm = c.take<float>(2 * (size_t)P.n_units);
+    return std::max<size_t>(c.off, 256);
+  }
+  P.status = c.take<uint32_t>(S);
+  P.tstar = c.take<uint32_t>(S);
+  P.rtie = c.take<uint32_t>(S);
+  P.tlo = c.take<uint32_t>(LU);
+  P.thi = c.take<uint32_t>(LU);
+  P.cntA = c.take<uint32_t>(LU);
+  P.cntC = c.take<uint32_t>(LU);
+  P.cntZ = c.take<uint32_t>(LU);
+  P.tsgn = c.take<uint32_t>(LU);
+  P.gtC = c.take<uint32_t>(LU);
+  P.eqC = c.take<uint32_t>(LU);
+  P.eqpre = c.take<uint32_t>(LU);
+  P.outoff = c.take<uint32_t>(LU);
+  P.uemit = c.take<uint4>(LU);
+  P.cval = c.take<uint32_t>(CC * LU);
+  P.cpos = c.take<uint16_t>(CC * LU);
+  P.stamps = c.take<uint64_t>(NSTAMP * std::max<size_t>(S, 1));  // (a call without COALAC_FLAG_STAMPS nulls it)
+  P.ghist = c.take<uint32_t>(HB2 * NG);
+  P.gcnt = c.take<uint32_t>(NG);
+  P.glist = c.take<uint2>(GCAP * NG);
+  P.gmm = c.take<float>(2 * NG);
+  P.sstate = c.take<uint4>(NL);
+  P.shhi = c.take<uint32_t>(NL);
+  return std::max<size_t>(c.off, 256);
 }
 
-WsLayout ws_layout(size_t S, size_t LU, size_t NG, size_t NL, uint32_t CC) {
-  WsLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    size_t r = o;
-    o = align_up(o + bytes, 256);
-    return r;
+// The plan's metadata tables on the host, and — listed once, in blob order — the Params pointer each becomes in the
+// plan's one device allocation. host null: returns the blob's size; else packs the vectors into `host` (a staging
+// buffer of that size, copied to `dev` by the caller) and points P's members into `dev`.
+struct PlanTables {
+  std::vector<SegDev> segs, lsegs, ssegs;
+  std::vector<UnitDev> units, lunits;
+  std::vector<uint32_t> small_list, large_list;
+  std::vector<uint4> groups, gseg;
+};
+
+size_t place_tables(const PlanTables& T, Params& P, uint8_t* host, const uint8_t* dev) {
+  Carver c{host};
+  auto put = [&](auto*& dst, const auto& v) {
+    using E = typename std::decay_t<decltype(v)>::value_type;
+    static_assert(std::is_same<decltype(dst), const E*&>::value, "table and pointer types differ");
+    E* h = c.take<E>(v.size());
+    if (!host) return;
+    if (!v.empty()) memcpy(h, v.data(), sizeof(E) * v.size());
+    dst = reinterpret_cast<const E*>(dev + (reinterpret_cast<uint8_t*>(h) - host));
   };
-  L.status = take(4 * S);
-  L.tstar = take(4 * S);
-  L.rtie = take(4 * S);
-  L.tlo = take(4 * LU);
-  L.thi = take(4 * LU);
-  L.cntA = take(4 * LU);
-  L.cntC = take(4 * LU);
-  L.cntZ = take(4 * LU);
-  L.tsgn = take(4 * LU);
-  L.gtC = take(4 * LU);
-  L.eqC = take(4 * LU);
-  L.eqpre = take(4 * LU);
-  L.outoff = take(4 * LU);
-  L.uemit = take(16 * LU);
-  L.cval = take(4 * (size_t)CC * LU);
-  L.cpos = take(2 * (size_t)CC * LU);
-  L.stamps = take(8 * NSTAMP * std::max<size_t>(S, 1));
-  L.ghist = take(4 * HB2 * NG);
-  L.gcnt = take(4 * NG);
-  L.glist = take(sizeof(uint2) * GCAP * NG);
-  L.gmm = take(8 * NG);
-  L.sstate = take(sizeof(uint4) * NL);
-  L.shhi = take(4 * NL);
-  L.total = std::max<size_t>(o, 256);
-  return L;
+  put(P.segs, T.segs);
+  put(P.units, T.units);
+  put(P.lunits, T.lunits);
+  put(P.small_list, T.small_list);
+  put(P.large_list, T.large_list);
+  put(P.lsegs, T.lsegs);
+  put(P.ssegs, T.ssegs);
+  put(P.groups, T.groups);
+  put(P.gseg, T.gseg);
+  return c.off + 256;  // (the blob ends in a 256-byte pad)
 }
+
+// Runtime flags -> template arguments, the one way: with_flags(f, a, b, ...) calls the generic lambda f with one
+// std::bool_constant per flag, so f's body names a kernel specialisation as k<a.value, b.value>. Every combination of
+// the flags passed is instantiated — a launch site passes only the flags whose every combination exists.
+template <typename F>
+auto with_flags(F&& f) {
+  return f();
+}
+template <typename F, typename... Rest>
+auto with_flags(F&& f, bool flag, Rest... rest) {
+  if (flag) return with_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...);
+  return with_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+// ... and the aggregate's mode, as a std::integral_constant<int, COALAC_AGG_*>
+template <typename F>
+auto with_agg_mode(int mode, F&& f) {
+  if (mode == COALAC_AGG_RECIP) return f(std::integral_constant<int, COALAC_AGG_RECIP>{});
+  if (mode == COALAC_AGG_SUM) return f(std::integral_constant<int, COALAC_AGG_SUM>{});
+  return f(std::integral_constant<int, COALAC_AGG_DIV>{});
+}
+
+// Small segments go beside the large ones' pipeline on a side stream once the batch is big enough for
+// the fork / join (~10-20 us) to pay off (>= 16384 large units, ~3 ResNet-50 updates).
+constexpr uint32_t FORK_MIN_LUNITS = 16384;
 
 }  // namespace
 
 struct coalac_plan {
   int device = -1;
   int bits = 8;
-  int nseg = 0;
-  uint32_t n_small = 0, n_large = 0, n_units = 0, n_lunits = 0;
-  uint32_t small_max = SMALL_MAX;  // segments of <= this many elements are "small" (encoded whole by one block)
-  uint32_t ccap = UNIT;  // candidate record slots per large unit
-  bool dense = false;    // every segment keeps all its elements: the dense codec (indices implied)
+  bool dense = false;        // every segment keeps all its elements: the dense codec (indices implied)
   bool dense_empty = false;  // a dense plan with a 0-element segment (keeps the separate k_dense_seg)
-  double rmax = 0.0;     // the largest k / n of the plan's segments
-  uint64_t span = 0, total_k = 0;
+  // Launch choices, decided once at plan creation. Two unit counts are in play: the encode kernels run over the large
+  // units only (a small segment is encoded whole by one block, off the streaming kernels' grid), the decode, dense and
+  // error-feedback kernels over all units — so "latency-bound" (<= LATENCY_PLAN_UNITS) is one predicate per count.
+  bool encode_latency = false;  // n_lunits: the sparse encode's kernel variants
+  bool decode_latency = false;  // n_units: the decode's and the dense codec's (and the default small-segment limit)
+  bool high_ratio = false;      // the largest k / n of the large segments > HIGH_RATIO: more record rows per round in
+                                // k_ghist / k_gwin / k_emit, and 8 entry chunks in registers in k_decode_lds
+  bool small_1k = false;        // small segments hold <= SMALL_MAX_LATENCY elements: k_scan's 16 KB small arena
+  bool fork_sized = false;      // small segments beside >= FORK_MIN_LUNITS large units: the encode forks them to a
+                                // side stream unless the call says COALAC_FLAG_NO_FORK
+  uint64_t span = 0, total_k = 0, ws_bytes = 0;
+  Params proto{};  // what every call's Params starts as: the metadata pointers (into meta), counts, levels and ccap
   void* meta = nullptr;
-  SegDev* segs = nullptr;
-  UnitDev* units = nullptr;
-  UnitDev* lunits = nullptr;
-  uint32_t* small_list = nullptr;
-  uint32_t* large_list = nullptr;
-  SegDev* lsegs = nullptr;
-  SegDev* ssegs = nullptr;
-  uint4* groups = nullptr;
-  uint4* gseg = nullptr;
-  uint32_t n_groups = 0;
   std::vector<SegDev> hsegs;  // host copy (aggregate validates the client-copy structure)
   // encode fork/join: k_small runs on `side`, concurrently with k_sample / k_scan on the caller's stream
   hipStream_t side = nullptr;
   hipEvent_t fork = nullptr, join = nullptr;
   std::mutex mu;  // serialises the (asynchronous) enqueue sequences that use side / fork / join
-  WsLayout ws{};
 };
 
 namespace {
@@ -3255,24 +3305,22 @@ int check_device(coalac_plan_t plan) {
   return COALAC_OK;
 }
 
-void fill_meta(Params& P, coalac_plan_t plan) {
-  P.segs = plan->segs;
-  P.units = plan->units;
-  P.lunits = plan->lunits;
-  P.small_list = plan->small_list;
-  P.large_list = plan->large_list;
-  P.lsegs = plan->lsegs;
-  P.ssegs = plan->ssegs;
-  P.groups = plan->groups;
-  P.gseg = plan->gseg;
-  P.n_groups = plan->n_groups;
-  P.nseg = (uint32_t)plan->nseg;
-  P.n_small = plan->n_small;
-  P.n_large = plan->n_large;
-  P.n_units = plan->n_units;
-  P.n_lunits = plan->n_lunits;
-  P.levels = plan->bits == 32 ? 0.0f : (float)((1u << plan->bits) - 1u);
-  P.ccap = plan->ccap;
+// shared by the entry points: the OR of some addresses (for one alignment test), the decoders' payload operands,
+// and the end of every launch sequence
+uintptr_t addr_bits(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c);
+}
+
+void set_payload(Params& P, const int32_t* d_idx, const void* d_vals, const float* d_mn, const float* d_scale) {
+  P.cidx = d_idx;
+  P.cvals = d_vals;
+  P.cmn = d_mn;
+  P.cscale = d_scale;
+}
+
+int launched() {
+  HIP_CHECK(hipGetLastError());
+  return COALAC_OK;
 }
 
 // Timing events of the _ev variants: hipEventRecord(ev[i], stream) at boundary i of a call (NULL array or entries:
@@ -3293,81 +3341,42 @@ struct Marks {
     if (rc_) return rc_;                \
   } while (0)
 
-// Small segments go beside the large ones' pipeline on a side stream once the batch is big enough for
-// the fork / join (~10-20 us) to pay off (>= 16384 large units, ~3 ResNet-50 updates).
-constexpr uint32_t FORK_MIN_LUNITS = 16384;
-
 // the dense encode: the min / max pass and the per-segment reduction between marks 0 and 1, the quantise stream
 // between 1 and 2 (where k_scan sits in a sparse encode)
 template <bool DELTA, bool RAW>
 int launch_dense_encode(const Params& P, coalac_plan_t plan, hipStream_t st, const Marks& marks) {
-  const dim3 g((plan->n_units + WAVES - 1) / WAVES);
-  const bool xcd = plan->n_units > LATENCY_PLAN_UNITS;
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  const bool xcd = !plan->decode_latency;
   MARK(0);
-  if (!RAW) {
-    if (xcd)
-      hipLaunchKernelGGL((k_dense_minmax<DELTA, true>), g, dim3(BLOCK), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_dense_minmax<DELTA, false>), g, dim3(BLOCK), 0, st, P);
-  }
-  if (plan->dense_empty) {  // a segment without units: k_dense_seg writes every segment's mn / scale
-    hipLaunchKernelGGL((k_dense_seg<RAW>), dim3(plan->nseg), dim3(BLOCK), 0, st, P);
-    MARK(1);
-    if (xcd)
-      hipLaunchKernelGGL((k_dense_quant<DELTA, RAW, true, false>), g, dim3(BLOCK), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_dense_quant<DELTA, RAW, false, false>), g, dim3(BLOCK), 0, st, P);
-  } else {
-    MARK(1);
-    if (xcd)
-      hipLaunchKernelGGL((k_dense_quant<DELTA, RAW, true, true>), g, dim3(BLOCK), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_dense_quant<DELTA, RAW, false, true>), g, dim3(BLOCK), 0, st, P);
-  }
+  if (!RAW)
+    with_flags([&](auto x) { hipLaunchKernelGGL((k_dense_minmax<DELTA, x.value>), g, dim3(BLOCK), 0, st, P); }, xcd);
+  // a segment without units: k_dense_seg writes every segment's mn / scale (else the quantise waves reduce their own)
+  if (plan->dense_empty) hipLaunchKernelGGL((k_dense_seg<RAW>), dim3(P.nseg), dim3(BLOCK), 0, st, P);
+  MARK(1);
+  with_flags(
+      [&](auto x, auto segred) {
+        hipLaunchKernelGGL((k_dense_quant<DELTA, RAW, x.value, segred.value>), g, dim3(BLOCK), 0, st, P);
+      },
+      xcd, !plan->dense_empty);
   MARK(2);
   MARK(3);
   MARK(4);
   return COALAC_OK;
 }
 
-template <bool RAW, bool HB>
-void launch_dense_decode(const Params& P, coalac_plan_t plan, hipStream_t st) {
-  const dim3 g((plan->n_units + WAVES - 1) / WAVES);
-  if (plan->n_units > LATENCY_PLAN_UNITS)
-    hipLaunchKernelGGL((k_dense_deq<RAW, HB, true>), g, dim3(BLOCK), 0, st, P);
-  else
-    hipLaunchKernelGGL((k_dense_deq<RAW, HB, false>), g, dim3(BLOCK), 0, st, P);
-}
-
-template <bool DELTA, bool RAW>
-void launch_emit(const Params& P, coalac_plan_t plan, hipStream_t st) {
-  const bool hi = plan->rmax > HIGH_RATIO;
-  if (plan->n_lunits <= LATENCY_PLAN_UNITS) {
-    constexpr uint32_t U = EMIT_UPW_LATENCY * WAVES;
-    const dim3 g((plan->n_lunits + U - 1) / U);
-    if (hi)
-      hipLaunchKernelGGL((k_emit<DELTA, RAW, EMIT_UPW_LATENCY, 4u>), g, dim3(BLOCK), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_emit<DELTA, RAW, EMIT_UPW_LATENCY, 1u>), g, dim3(BLOCK), 0, st, P);
-  } else {
-    constexpr uint32_t U = EMIT_UPW * WAVES;
-    const dim3 g((plan->n_lunits + U - 1) / U);
-    if (hi)
-      hipLaunchKernelGGL((k_emit<DELTA, RAW, EMIT_UPW, 4u>), g, dim3(BLOCK), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_emit<DELTA, RAW, EMIT_UPW, 1u>), g, dim3(BLOCK), 0, st, P);
-  }
-}
-
+// The sparse encode. By plan class (the file header lists the kernels):
+//   latency-bound (encode_latency):  k_sample -> k_scan with the small segments in its first blocks -> the select
+//                                    chain and k_emit in their *_LAT geometries
+//   batch:                           k_presel (samplers + small segments) -> k_scan over large units only -> ...
+//   fork class (fork_sized, unless the call says COALAC_FLAG_NO_FORK): k_small on the plan's side stream beside
+//                                    k_sample -> k_scan -> ..., joined after k_emit
+// A plan without small segments runs k_sample alone; one without large segments only its small-segment kernel.
 template <bool DELTA, bool RAW>
 int launch_encode(const Params& P, coalac_plan_t plan, hipStream_t st, const Marks& marks) {
-  const uint32_t gu = (plan->n_lunits + WAVES - 1) / WAVES;
-  // small segments: forked beside k_sample / k_scan on the plan's side stream (big batches), beside the samplers in
-  // k_presel (other batches), or in k_scan's first blocks beside the streaming waves (latency-bound plans: k_sample
-  // alone ahead of it)
-  const bool fork = plan->n_small && plan->n_lunits >= FORK_MIN_LUNITS && !(P.flags & COALAC_FLAG_NO_FORK);
-  const bool presel = !fork && plan->n_small;
-  const bool small_in_scan = presel && plan->n_lunits <= LATENCY_PLAN_UNITS;
+  const bool lat = plan->encode_latency;
+  const bool fork = plan->fork_sized && !(P.flags & COALAC_FLAG_NO_FORK);
+  const bool presel = !fork && P.n_small;
+  const bool small_in_scan = presel && lat;
   Params Q = P;
   Q.scan_small = 0u;
   std::unique_lock<std::mutex> lk(plan->mu, std::defer_lock);
@@ -3385,54 +3394,110 @@ int launch_encode(const Params& P, coalac_plan_t plan, hipStream_t st, const Mar
   if (fork) {
     HIP_CHECK(hipEventRecord(plan->fork, st));
     HIP_CHECK(hipStreamWaitEvent(plan->side, plan->fork, 0));
-    hipLaunchKernelGGL((k_small<DELTA, RAW>), dim3(plan->n_small), dim3(BLOCK), 0, plan->side, P);
+    hipLaunchKernelGGL((k_small<DELTA, RAW>), dim3(P.n_small), dim3(BLOCK), 0, plan->side, P);
     HIP_CHECK(hipEventRecord(plan->join, plan->side));
   }
   if (presel && !small_in_scan)
-    hipLaunchKernelGGL((k_presel<DELTA, RAW>), dim3(plan->n_large + plan->n_small), dim3(BLOCK), 0, st, P);
-  else if (plan->n_large && plan->n_lunits <= LATENCY_PLAN_UNITS)
-    hipLaunchKernelGGL((k_sample<DELTA, RAW, SAMPLE_NT_LAT>), dim3(plan->n_large), dim3(SAMPLE_NT_LAT), 0, st, P);
-  else if (plan->n_large)
-    hipLaunchKernelGGL((k_sample<DELTA, RAW, BLOCK>), dim3(plan->n_large), dim3(BLOCK), 0, st, P);
+    hipLaunchKernelGGL((k_presel<DELTA, RAW>), dim3(P.n_large + P.n_small), dim3(BLOCK), 0, st, P);
+  else if (P.n_large && lat)
+    hipLaunchKernelGGL((k_sample<DELTA, RAW, SAMPLE_NT_LAT>), dim3(P.n_large), dim3(SAMPLE_NT_LAT), 0, st, P);
+  else if (P.n_large)
+    hipLaunchKernelGGL((k_sample<DELTA, RAW, BLOCK>), dim3(P.n_large), dim3(BLOCK), 0, st, P);
   MARK(1);
   if (small_in_scan) {
-    Q.scan_small = plan->n_small;
-    const dim3 gs((plan->n_lunits + SCAN_NT_LAT / 64 - 1) / (SCAN_NT_LAT / 64) + plan->n_small);
-    if (plan->small_max <= SMALL_MAX_LATENCY)
+    Q.scan_small = P.n_small;
+    const dim3 gs(ceil_div(P.n_lunits, SCAN_NT_LAT / 64) + P.n_small);
+    if (plan->small_1k)
       hipLaunchKernelGGL((k_scan<DELTA, RAW, true, SCAN_WPE_LAT_1K, SCAN_NB_LAT, SCAN_NT_LAT, SMALL_MAX_LATENCY>), gs,
                          dim3(SCAN_NT_LAT), 0, st, Q);
     else
       hipLaunchKernelGGL((k_scan<DELTA, RAW, true, SCAN_WPE_LAT, SCAN_NB_LAT, SCAN_NT_LAT>), gs, dim3(SCAN_NT_LAT), 0, st,
                          Q);
-  } else if (gu) {
-    hipLaunchKernelGGL((k_scan<DELTA, RAW, false, SCAN_WPE, SCAN_NB, SCAN_NT>),
-                       dim3((plan->n_lunits + SCAN_NT / 64 - 1) / (SCAN_NT / 64)), dim3(SCAN_NT), 0, st, Q);
+  } else if (P.n_lunits) {
+    hipLaunchKernelGGL((k_scan<DELTA, RAW, false, SCAN_WPE, SCAN_NB, SCAN_NT>), dim3(ceil_div(P.n_lunits, SCAN_NT / 64)),
+                       dim3(SCAN_NT), 0, st, Q);
   }
   MARK(2);
-  if (plan->n_large) {
-    const bool lat = plan->n_lunits <= LATENCY_PLAN_UNITS, hr = plan->rmax > HIGH_RATIO;
-    if (lat)
-      hipLaunchKernelGGL((k_ghist<GHIST_NT_LAT, true>), dim3(plan->n_groups), dim3(GHIST_NT_LAT), 0, st, P);
-    else if (hr)
-      hipLaunchKernelGGL((k_ghist<BLOCK, false, true>), dim3(plan->n_groups), dim3(BLOCK), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_ghist<BLOCK, false>), dim3(plan->n_groups), dim3(BLOCK), 0, st, P);
-    if (lat)
-      hipLaunchKernelGGL((k_gwin<GWIN_NT_LAT, true>), dim3(plan->n_groups), dim3(GWIN_NT_LAT), 0, st, P);
-    else if (hr)
-      hipLaunchKernelGGL((k_gwin<BLOCK, false, true>), dim3(plan->n_groups), dim3(BLOCK), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_gwin<BLOCK, false>), dim3(plan->n_groups), dim3(BLOCK), 0, st, P);
-    if (lat)
-      hipLaunchKernelGGL((k_select<DELTA, RAW, SEL_NT_LAT>), dim3(plan->n_large), dim3(SEL_NT_LAT), 0, st, P);
-    else
-      hipLaunchKernelGGL((k_select<DELTA, RAW>), dim3(plan->n_large), dim3(SEL_NT), 0, st, P);
+  if (P.n_large && lat) {  // the speculative sweeps (no high-ratio variant of them)
+    hipLaunchKernelGGL((k_ghist<GHIST_NT_LAT, true>), dim3(P.n_groups), dim3(GHIST_NT_LAT), 0, st, P);
+    hipLaunchKernelGGL((k_gwin<GWIN_NT_LAT, true>), dim3(P.n_groups), dim3(GWIN_NT_LAT), 0, st, P);
+    hipLaunchKernelGGL((k_select<DELTA, RAW, SEL_NT_LAT>), dim3(P.n_large), dim3(SEL_NT_LAT), 0, st, P);
+  } else if (P.n_large) {
+    with_flags(
+        [&](auto hr) {
+          hipLaunchKernelGGL((k_ghist<BLOCK, false, hr.value>), dim3(P.n_groups), dim3(BLOCK), 0, st, P);
+          hipLaunchKernelGGL((k_gwin<BLOCK, false, hr.value>), dim3(P.n_groups), dim3(BLOCK), 0, st, P);
+        },
+        plan->high_ratio);
+    hipLaunchKernelGGL((k_select<DELTA, RAW>), dim3(P.n_large), dim3(SEL_NT), 0, st, P);
   }
   MARK(3);
-  if (plan->n_large) launch_emit<DELTA, RAW>(P, plan, st);
+  if (P.n_large)
+    with_flags(
+        [&](auto l, auto hr) {
+          constexpr uint32_t UPW = l.value ? EMIT_UPW_LAT : EMIT_UPW, TR = hr.value ? 4u : 1u;
+          hipLaunchKernelGGL((k_emit<DELTA, RAW, UPW, TR>), dim3(ceil_div(P.n_lunits, UPW * WAVES)), dim3(BLOCK), 0, st, P);
+        },
+        lat, plan->high_ratio);
   if (fork) HIP_CHECK(hipStreamWaitEvent(st, plan->join, 0));
   MARK(4);
   return COALAC_OK;
+}
+
+int encode_impl(coalac_plan_t plan, const float* d_in, const float* const* d_inptr, const float* d_base,
+                int32_t* d_idx, void* d_vals, float* d_mn, float* d_scale, uint32_t* d_ustart, void* d_ws,
+                uint64_t ws_bytes, unsigned flags, void* stream, const Marks& marks) {
+  if (!plan) return fail(COALAC_EINVAL, "coalac_encode: plan is NULL");
+  if (plan->proto.nseg == 0) return COALAC_OK;
+  if (!d_mn || !d_scale) return fail(COALAC_EINVAL, "coalac_encode: mn/scale pointers are NULL");
+  if (plan->span && !d_in && !d_inptr) return fail(COALAC_EINVAL, "coalac_encode: input pointer is NULL");
+  if (plan->total_k && (!(d_idx || plan->dense) || !d_vals))
+    return fail(COALAC_EINVAL, "coalac_encode: idx/vals pointers are NULL (idx may be NULL for a dense plan only)");
+  if (addr_bits(d_in, d_base) & 15) return fail(COALAC_EINVAL, "coalac_encode: input/base must be 16-byte aligned");
+  if (addr_bits(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_encode: ustart must be 4-byte aligned");
+  if (!d_ws || ws_bytes < plan->ws_bytes)
+    return fail(COALAC_EWORKSPACE, "coalac_encode: workspace %llu < required %llu", (unsigned long long)ws_bytes,
+                (unsigned long long)plan->ws_bytes);
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.in = d_in;
+  P.inptr = d_inptr;
+  P.base = d_base;
+  P.idx = d_idx;
+  P.vals = d_vals;
+  P.mn = d_mn;
+  P.scale = d_scale;
+  P.ustart_out = d_ustart;
+  P.flags = flags;
+  carve_workspace(P, plan->dense, d_ws);
+  if (!(flags & COALAC_FLAG_STAMPS)) P.stamps = nullptr;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = with_flags(
+      [&](auto delta, auto raw) {
+        return plan->dense ? launch_dense_encode<delta.value, raw.value>(P, plan, st, marks)
+                           : launch_encode<delta.value, raw.value>(P, plan, st, marks);
+      },
+      d_base != nullptr, plan->bits == 32);
+  return rc ? rc : launched();
+}
+
+// The write-once decode (k_decode_lds) of a whole plan: batches one wave per unit in two 8-row passes (4-row in
+// delta mode) with non-temporal stores and the XCD-aware order; latency-bound plans DECODE_WPU_LAT waves per unit
+// (one pass each: twice the waves, each with half the work, for a launch of one update's ~6.5 k units).
+// HR: plans whose segments keep more than ~1.5 % (more than 64 entries in a unit on average) hold 8 entry chunks in
+// registers (from ratio 0.02, the plan's high_ratio: C3 at ratio 0.1, decode 0.63 -> 0.37 ms)
+template <bool RAW, bool HB, bool HR>
+void launch_decode_lds(const Params& P, coalac_plan_t plan, hipStream_t st) {
+  constexpr uint32_t DW = DECODE_NT / 64, NCH = HR ? 8u : 1u;
+  if (plan->decode_latency) {
+    constexpr uint32_t W = DECODE_WPU_LAT, Q = HB ? DECODE_QROWS_BASE : UNIT_IT / DECODE_WPU_LAT;
+    hipLaunchKernelGGL((k_decode_lds<RAW, HB, W, (Q < 8u ? Q : 8u), DECODE_SAUX_LAT, false, NCH>),
+                       dim3(ceil_div(P.n_units * W, DW)), dim3(DECODE_NT), 0, st, P);
+  } else {
+    hipLaunchKernelGGL((k_decode_lds<RAW, HB, 1u, HB ? DECODE_QROWS_BASE : DECODE_QROWS, STORE_AUX, true, NCH>),
+                       dim3(ceil_div(P.n_units, DW)), dim3(DECODE_NT), 0, st, P);
+  }
 }
 
 }  // namespace
@@ -3449,15 +3514,16 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
   if (nseg < 0 || (nseg > 0 && !h_segs)) return fail(COALAC_EINVAL, "coalac_plan_create: bad segment table");
   if (!((bits >= 1 && bits <= 8) || bits == 32)) return fail(COALAC_EBITS, "unsupported bits=%d (1..8 or 32)", bits);
 
-  std::vector<SegDev> segs(nseg);
-  std::vector<UnitDev> units, lunits;
-  std::vector<uint4> groups, gseg;
-  std::vector<uint32_t> small_list, large_list;
+  PlanTables T;
+  T.segs.resize(nseg);
   uint64_t span = 0, total_k = 0;
   std::vector<std::pair<uint64_t, uint64_t>> in_r, out_r;
-  uint64_t est_units = 0;
-  for (int s = 0; s < nseg; ++s) est_units += (std::min<uint64_t>(h_segs[s].n, 1ull << 31) + UNIT - 1) / UNIT;
-  uint32_t small_max = est_units <= LATENCY_PLAN_UNITS ? SMALL_MAX_LATENCY : SMALL_MAX_BATCH;
+  // the table's unit count, before the units exist: it classes the plan, and the class sets the small-segment limit
+  // the units are built under (an n the validation below rejects is clamped, so the sum cannot wrap)
+  uint64_t n_units = 0;
+  for (int s = 0; s < nseg; ++s) n_units += (std::min<uint64_t>(h_segs[s].n, 1ull << 31) + UNIT - 1) / UNIT;
+  const bool decode_latency = n_units <= LATENCY_PLAN_UNITS;
+  uint32_t small_max = decode_latency ? SMALL_MAX_LATENCY : SMALL_MAX_BATCH;
   if (const char* e = getenv("COALAC_SMALL_MAX")) small_max = std::min<uint32_t>(std::max(atoi(e), 1024), SMALL_MAX);
   for (int s = 0; s < nseg; ++s) {
     const coalac_seg_t& g = h_segs[s];
@@ -3473,9 +3539,9 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
     d.out_off = g.out_off;
     d.n = (uint32_t)g.n;
     d.k = (uint32_t)g.k;
-    d.unit_begin = (uint32_t)units.size();
+    d.unit_begin = (uint32_t)T.units.size();
     const bool large = g.n > small_max;
-    d.lu_begin = large ? (uint32_t)lunits.size() : 0u;
+    d.lu_begin = large ? (uint32_t)T.lunits.size() : 0u;
     for (uint64_t st = 0; st < g.n; st += UNIT) {
       UnitDev u{};
       u.off = g.in_off + st;
@@ -3485,20 +3551,21 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
       u.k = (uint32_t)g.k;
       u.len = (uint16_t)std::min<uint64_t>(UNIT, g.n - st);
       u.last = st + UNIT >= g.n ? 1 : 0;
-      units.push_back(u);
-      if (large) lunits.push_back(u);
+      T.units.push_back(u);
+      if (large) T.lunits.push_back(u);
     }
-    d.unit_end = (uint32_t)units.size();
+    d.unit_end = (uint32_t)T.units.size();
     if (large) {
-      d.g_begin = (uint32_t)groups.size();
+      d.g_begin = (uint32_t)T.groups.size();
       const uint32_t nu = d.unit_end - d.unit_begin;
       for (uint32_t g0 = 0; g0 < nu; g0 += GU) {
-        groups.push_back(make_uint4((uint32_t)large_list.size(), d.lu_begin + g0, std::min(GU, nu - g0), (uint32_t)s));
-        gseg.push_back(make_uint4(d.lu_begin, nu, (uint32_t)g.k, d.g_begin));
+        T.groups.push_back(make_uint4((uint32_t)T.large_list.size(), d.lu_begin + g0, std::min(GU, nu - g0), (uint32_t)s));
+        T.gseg.push_back(make_uint4(d.lu_begin, nu, (uint32_t)g.k, d.g_begin));
       }
     }
-    (large ? large_list : small_list).push_back((uint32_t)s);
-    segs[s] = d;
+    (large ? T.large_list : T.small_list).push_back((uint32_t)s);
+    (large ? T.lsegs : T.ssegs).push_back(d);
+    T.segs[s] = d;
     if (g.n) {
       span = std::max<uint64_t>(span, g.in_off + g.n);
       total_k = std::max<uint64_t>(total_k, g.out_off + g.k);
@@ -3506,7 +3573,8 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
       out_r.push_back({g.out_off, g.out_off + g.k});
     }
   }
-  if (lunits.size() >= (1ull << 32) / UNIT) return fail(COALAC_EINVAL, "plan too large (%zu large units)", lunits.size());
+  if (T.lunits.size() >= (1ull << 32) / UNIT)
+    return fail(COALAC_EINVAL, "plan too large (%zu large units)", T.lunits.size());
   auto overlaps = [](std::vector<std::pair<uint64_t, uint64_t>>& r) {
     std::sort(r.begin(), r.end());
     for (size_t i = 1; i < r.size(); ++i)
@@ -3521,75 +3589,48 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
   coalac_plan* p = new coalac_plan();
   p->device = dev;
   p->bits = bits;
-  p->nseg = nseg;
-  p->n_small = (uint32_t)small_list.size();
-  p->n_large = (uint32_t)large_list.size();
-  p->n_units = (uint32_t)units.size();
-  p->n_lunits = (uint32_t)lunits.size();
-  p->n_groups = (uint32_t)groups.size();
   p->span = span;
   p->total_k = total_k;
-  p->hsegs = segs;
+  p->hsegs = T.segs;
+  Params& M = p->proto;
+  M.nseg = (uint32_t)nseg;
+  M.n_small = (uint32_t)T.small_list.size();
+  M.n_large = (uint32_t)T.large_list.size();
+  M.n_units = (uint32_t)T.units.size();
+  M.n_lunits = (uint32_t)T.lunits.size();
+  M.n_groups = (uint32_t)T.groups.size();
+  M.levels = bits == 32 ? 0.0f : (float)((1u << bits) - 1u);
   // record slots per large unit: the candidates a unit can expect at the plan's largest ratio (kept
   // share + the sampled band + margin), so the workspace is ~1 B/element at ratio 0.01 instead of 8
   double rmax = 0.0;
-  for (uint32_t s2 : large_list) rmax = std::max(rmax, (double)segs[s2].k / (double)segs[s2].n);
-  p->rmax = rmax;
+  for (const SegDev& d : T.lsegs) rmax = std::max(rmax, (double)d.k / (double)d.n);
   uint32_t ccap = (uint32_t)align_up((size_t)(UNIT * std::min(1.0, 2.0 * rmax + 0.05) + 256.0), 64);
   if (const char* e = getenv("COALAC_CCAP")) ccap = (uint32_t)atoi(e);  // tests: force overflow
-  ccap = std::max<uint32_t>(STAGE_CAP, std::min<uint32_t>(UNIT, ccap));
-  p->ccap = ccap;
-  p->small_max = small_max;
+  M.ccap = std::max<uint32_t>(STAGE_CAP, std::min<uint32_t>(UNIT, ccap));
   p->dense = true;
-  for (const SegDev& d : segs) p->dense = p->dense && d.k == d.n;
-  for (const SegDev& d : segs) p->dense_empty = p->dense_empty || d.unit_begin == d.unit_end;
-  p->ws = p->dense ? ws_layout_dense(units.size())
-                   : ws_layout((size_t)nseg, lunits.size(), groups.size(), large_list.size(), ccap);
+  for (const SegDev& d : T.segs) p->dense = p->dense && d.k == d.n;
+  for (const SegDev& d : T.segs) p->dense_empty = p->dense_empty || d.unit_begin == d.unit_end;
+  p->encode_latency = M.n_lunits <= LATENCY_PLAN_UNITS;
+  p->decode_latency = decode_latency;
+  p->high_ratio = rmax > HIGH_RATIO;
+  p->small_1k = small_max <= SMALL_MAX_LATENCY;
+  p->fork_sized = M.n_small && M.n_lunits >= FORK_MIN_LUNITS;
+  p->ws_bytes = carve_workspace(M, p->dense, nullptr);
 
-  const size_t o_segs = 0;
-  const size_t o_units = align_up(o_segs + sizeof(SegDev) * segs.size(), 256);
-  const size_t o_lunits = align_up(o_units + sizeof(UnitDev) * units.size(), 256);
-  const size_t o_small = align_up(o_lunits + sizeof(UnitDev) * lunits.size(), 256);
-  const size_t o_large = align_up(o_small + 4 * small_list.size(), 256);
-  std::vector<SegDev> lsegs, ssegs;
-  for (uint32_t s2 : large_list) lsegs.push_back(segs[s2]);
-  for (uint32_t s2 : small_list) ssegs.push_back(segs[s2]);
-  const size_t o_lsegs = align_up(o_large + 4 * large_list.size(), 256);
-  const size_t o_ssegs = align_up(o_lsegs + sizeof(SegDev) * lsegs.size(), 256);
-  const size_t o_grp = align_up(o_ssegs + sizeof(SegDev) * ssegs.size(), 256);
-  const size_t o_gseg = align_up(o_grp + sizeof(uint4) * groups.size(), 256);
-  const size_t bytes = align_up(o_gseg + sizeof(uint4) * gseg.size(), 256) + 256;
+  const size_t bytes = place_tables(T, M, nullptr, nullptr);
   std::vector<uint8_t> host(bytes, 0);
-  if (!segs.empty()) memcpy(host.data() + o_segs, segs.data(), sizeof(SegDev) * segs.size());
-  if (!units.empty()) memcpy(host.data() + o_units, units.data(), sizeof(UnitDev) * units.size());
-  if (!lunits.empty()) memcpy(host.data() + o_lunits, lunits.data(), sizeof(UnitDev) * lunits.size());
-  if (!small_list.empty()) memcpy(host.data() + o_small, small_list.data(), 4 * small_list.size());
-  if (!large_list.empty()) memcpy(host.data() + o_large, large_list.data(), 4 * large_list.size());
-  if (!lsegs.empty()) memcpy(host.data() + o_lsegs, lsegs.data(), sizeof(SegDev) * lsegs.size());
-  if (!ssegs.empty()) memcpy(host.data() + o_ssegs, ssegs.data(), sizeof(SegDev) * ssegs.size());
-  if (!groups.empty()) memcpy(host.data() + o_grp, groups.data(), sizeof(uint4) * groups.size());
-  if (!gseg.empty()) memcpy(host.data() + o_gseg, gseg.data(), sizeof(uint4) * gseg.size());
   hipError_t e = hipMalloc(&p->meta, bytes);
   if (e != hipSuccess) {
     delete p;
     return fail(COALAC_ENOMEM, "hipMalloc(%zu) for plan metadata failed: %s", bytes, hipGetErrorString(e));
   }
+  place_tables(T, M, host.data(), static_cast<const uint8_t*>(p->meta));
   e = hipMemcpy(p->meta, host.data(), bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     (void)hipFree(p->meta);
     delete p;
     return fail(COALAC_EHIP, "hipMemcpy of plan metadata failed: %s", hipGetErrorString(e));
   }
-  uint8_t* m = static_cast<uint8_t*>(p->meta);
-  p->segs = reinterpret_cast<SegDev*>(m + o_segs);
-  p->units = reinterpret_cast<UnitDev*>(m + o_units);
-  p->lunits = reinterpret_cast<UnitDev*>(m + o_lunits);
-  p->small_list = reinterpret_cast<uint32_t*>(m + o_small);
-  p->large_list = reinterpret_cast<uint32_t*>(m + o_large);
-  p->lsegs = reinterpret_cast<SegDev*>(m + o_lsegs);
-  p->ssegs = reinterpret_cast<SegDev*>(m + o_ssegs);
-  p->groups = reinterpret_cast<uint4*>(m + o_grp);
-  p->gseg = reinterpret_cast<uint4*>(m + o_gseg);
   *out = p;
   return COALAC_OK;
 }
@@ -3610,100 +3651,12 @@ int coalac_plan_destroy(coalac_plan_t plan) {
 
 int coalac_plan_query(coalac_plan_t plan, uint64_t* ws_bytes, uint64_t* total_k, uint64_t* span, uint64_t* n_units) {
   if (!plan) return fail(COALAC_EINVAL, "coalac_plan_query: plan is NULL");
-  if (ws_bytes) *ws_bytes = plan->ws.total;
+  if (ws_bytes) *ws_bytes = plan->ws_bytes;
   if (total_k) *total_k = plan->total_k;
   if (span) *span = plan->span;
-  if (n_units) *n_units = plan->n_units;
+  if (n_units) *n_units = plan->proto.n_units;
   return COALAC_OK;
 }
-
-}  // extern "C"
-
-namespace {
-int encode_impl(coalac_plan_t plan, const float* d_in, const float* const* d_inptr, const float* d_base,
-                int32_t* d_idx, void* d_vals, float* d_mn, float* d_scale, uint32_t* d_ustart, void* d_ws,
-                uint64_t ws_bytes, unsigned flags, void* stream, const Marks& marks) {
-  if (!plan) return fail(COALAC_EINVAL, "coalac_encode: plan is NULL");
-  if (plan->nseg == 0) return COALAC_OK;
-  if (!d_mn || !d_scale) return fail(COALAC_EINVAL, "coalac_encode: mn/scale pointers are NULL");
-  if (plan->span && !d_in && !d_inptr) return fail(COALAC_EINVAL, "coalac_encode: input pointer is NULL");
-  if (plan->total_k && (!(d_idx || plan->dense) || !d_vals))
-    return fail(COALAC_EINVAL, "coalac_encode: idx/vals pointers are NULL (idx may be NULL for a dense plan only)");
-  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_base)) & 15)
-    return fail(COALAC_EINVAL, "coalac_encode: input/base must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_encode: ustart must be 4-byte aligned");
-  if (!d_ws || ws_bytes < plan->ws.total)
-    return fail(COALAC_EWORKSPACE, "coalac_encode: workspace %llu < required %llu", (unsigned long long)ws_bytes,
-                (unsigned long long)plan->ws.total);
-  int rc = check_device(plan);
-  if (rc) return rc;
-  Params P{};
-  fill_meta(P, plan);
-  P.in = d_in;
-  P.inptr = d_inptr;
-  P.base = d_base;
-  P.idx = d_idx;
-  P.vals = d_vals;
-  P.mn = d_mn;
-  P.scale = d_scale;
-  P.ustart_out = d_ustart;
-  P.flags = flags;
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
-  const WsLayout& L = plan->ws;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool delta = d_base != nullptr, raw = plan->bits == 32;
-  if (plan->dense) {
-    P.umm = reinterpret_cast<float*>(w + L.umm);
-    if (delta && raw)
-      rc = launch_dense_encode<true, true>(P, plan, st, marks);
-    else if (delta)
-      rc = launch_dense_encode<true, false>(P, plan, st, marks);
-    else if (raw)
-      rc = launch_dense_encode<false, true>(P, plan, st, marks);
-    else
-      rc = launch_dense_encode<false, false>(P, plan, st, marks);
-    if (rc) return rc;
-    HIP_CHECK(hipGetLastError());
-    return COALAC_OK;
-  }
-  P.tstar = reinterpret_cast<uint32_t*>(w + L.tstar);
-  P.rtie = reinterpret_cast<uint32_t*>(w + L.rtie);
-  P.status = reinterpret_cast<uint32_t*>(w + L.status);
-  P.tlo = reinterpret_cast<uint32_t*>(w + L.tlo);
-  P.thi = reinterpret_cast<uint32_t*>(w + L.thi);
-  P.cntA = reinterpret_cast<uint32_t*>(w + L.cntA);
-  P.cntC = reinterpret_cast<uint32_t*>(w + L.cntC);
-  P.cntZ = reinterpret_cast<uint32_t*>(w + L.cntZ);
-  P.tsgn = reinterpret_cast<uint32_t*>(w + L.tsgn);
-  P.gtC = reinterpret_cast<uint32_t*>(w + L.gtC);
-  P.eqC = reinterpret_cast<uint32_t*>(w + L.eqC);
-  P.eqpre = reinterpret_cast<uint32_t*>(w + L.eqpre);
-  P.outoff = reinterpret_cast<uint32_t*>(w + L.outoff);
-  P.uemit = reinterpret_cast<uint4*>(w + L.uemit);
-  P.cval = reinterpret_cast<uint32_t*>(w + L.cval);
-  P.cpos = reinterpret_cast<uint16_t*>(w + L.cpos);
-  P.stamps = (flags & COALAC_FLAG_STAMPS) ? reinterpret_cast<uint64_t*>(w + L.stamps) : nullptr;
-  P.ghist = reinterpret_cast<uint32_t*>(w + L.ghist);
-  P.gcnt = reinterpret_cast<uint32_t*>(w + L.gcnt);
-  P.glist = reinterpret_cast<uint2*>(w + L.glist);
-  P.gmm = reinterpret_cast<float*>(w + L.gmm);
-  P.sstate = reinterpret_cast<uint4*>(w + L.sstate);
-  P.shhi = reinterpret_cast<uint32_t*>(w + L.shhi);
-  if (delta && raw)
-    rc = launch_encode<true, true>(P, plan, st, marks);
-  else if (delta)
-    rc = launch_encode<true, false>(P, plan, st, marks);
-  else if (raw)
-    rc = launch_encode<false, true>(P, plan, st, marks);
-  else
-    rc = launch_encode<false, false>(P, plan, st, marks);
-  if (rc) return rc;
-  HIP_CHECK(hipGetLastError());
-  return COALAC_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int coalac_encode_ev(coalac_plan_t plan, const float* d_in, const float* d_base, int32_t* d_idx,
                      void* d_vals, float* d_mn, float* d_scale, uint32_t* d_ustart, void* d_ws, uint64_t ws_bytes,
@@ -3715,7 +3668,7 @@ int coalac_encode_ev(coalac_plan_t plan, const float* d_in, const float* d_base,
 int coalac_encode_segptr(coalac_plan_t plan, const float* const* d_seg_in, const float* d_base, int32_t* d_idx,
                          void* d_vals, float* d_mn, float* d_scale, uint32_t* d_ustart, void* d_ws, uint64_t ws_bytes,
                          unsigned flags, void* stream) {
-  if (plan && plan->nseg && !d_seg_in) return fail(COALAC_EINVAL, "coalac_encode_segptr: d_seg_in is NULL");
+  if (plan && plan->proto.nseg && !d_seg_in) return fail(COALAC_EINVAL, "coalac_encode_segptr: d_seg_in is NULL");
   return encode_impl(plan, nullptr, d_seg_in, d_base, d_idx, d_vals, d_mn, d_scale, d_ustart, d_ws, ws_bytes, flags,
                      stream, Marks{nullptr, 0});
 }
@@ -3727,44 +3680,11 @@ int coalac_encode(coalac_plan_t plan, const float* d_in, const float* d_base, in
                           nullptr);
 }
 
-}  // extern "C"
-
-namespace {
-// The write-once decode (k_decode_lds) of a whole plan: batches one wave per unit in two 8-row passes (4-row in
-// delta mode) with non-temporal stores and the XCD-aware order; latency-bound plans DECODE_WPU_LAT waves per unit
-// (one pass each: twice the waves, each with half the work, for a launch of one update's ~6.5 k units).
-template <bool RAW, bool HB, uint32_t NCH>
-void launch_decode_lds_n(const Params& P, coalac_plan_t plan, hipStream_t st) {
-  constexpr uint32_t DW = DECODE_NT / 64;
-  if (plan->n_units <= LATENCY_PLAN_UNITS) {
-    constexpr uint32_t W = DECODE_WPU_LAT, Q = HB ? DECODE_QROWS_BASE : UNIT_IT / DECODE_WPU_LAT;
-    hipLaunchKernelGGL((k_decode_lds<RAW, HB, W, (Q < 8u ? Q : 8u), DECODE_SAUX_LAT, false, NCH>),
-                       dim3((plan->n_units * W + DW - 1) / DW), dim3(DECODE_NT), 0, st, P);
-  } else {
-    hipLaunchKernelGGL((k_decode_lds<RAW, HB, 1u, HB ? DECODE_QROWS_BASE : DECODE_QROWS, STORE_AUX, true, NCH>),
-                       dim3((plan->n_units + DW - 1) / DW), dim3(DECODE_NT), 0, st, P);
-  }
-}
-
-// plans whose segments keep more than ~1.5 % (more than 64 entries in a unit on average) hold 8 entry chunks in
-// registers (from ratio 0.02: C3 at ratio 0.1, decode 0.63 -> 0.37 ms)
-constexpr double DECODE_NCH_RATIO = HIGH_RATIO;
-template <bool RAW, bool HB>
-void launch_decode_lds(const Params& P, coalac_plan_t plan, hipStream_t st) {
-  if (plan->rmax > DECODE_NCH_RATIO)
-    launch_decode_lds_n<RAW, HB, 8u>(P, plan, st);
-  else
-    launch_decode_lds_n<RAW, HB, 1u>(P, plan, st);
-}
-}  // namespace
-
-extern "C" {
-
 int coalac_decode_ev(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
                      const float* d_scale, const uint32_t* d_ustart, const float* d_base, float* d_out, void* stream,
                      void* const* events) {
   if (!plan) return fail(COALAC_EINVAL, "coalac_decode: plan is NULL");
-  if (plan->n_units == 0) return COALAC_OK;
+  if (plan->proto.n_units == 0) return COALAC_OK;
   if (!d_out) return fail(COALAC_EINVAL, "coalac_decode: output pointer is NULL");
   // a sparse plan decodes every unit's entry range from the per-unit starts (wire v2; the host computes them for a
   // v1 payload); a dense plan's indices and starts are implied (neither is read)
@@ -3773,17 +3693,12 @@ int coalac_decode_ev(coalac_plan_t plan, const int32_t* d_idx, const void* d_val
                 "starts of wire v2)");
   if (plan->total_k && plan->bits != 32 && (!d_mn || !d_scale))
     return fail(COALAC_EINVAL, "coalac_decode: mn/scale pointers are NULL");
-  if ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_base)) & 15)
-    return fail(COALAC_EINVAL, "coalac_decode: output/base must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_decode: ustart must be 4-byte aligned");
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_decode: output/base must be 16-byte aligned");
+  if (addr_bits(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_decode: ustart must be 4-byte aligned");
   int rc = check_device(plan);
   if (rc) return rc;
-  Params P{};
-  fill_meta(P, plan);
-  P.cidx = d_idx;
-  P.cvals = d_vals;
-  P.cmn = d_mn;
-  P.cscale = d_scale;
+  Params P = plan->proto;
+  set_payload(P, d_idx, d_vals, d_mn, d_scale);
   P.base = d_base;
   P.out = d_out;
   P.ustart = d_ustart;
@@ -3792,21 +3707,18 @@ int coalac_decode_ev(coalac_plan_t plan, const int32_t* d_idx, const void* d_val
   const Marks marks{events, 3};
   MARK(0);
   MARK(1);
-#define DISPATCH(F, ...)                                   \
-  do {                                                     \
-    if (raw && hb) F<true, true>(__VA_ARGS__);             \
-    else if (raw) F<true, false>(__VA_ARGS__);             \
-    else if (hb) F<false, true>(__VA_ARGS__);              \
-    else F<false, false>(__VA_ARGS__);                     \
-  } while (0)
-  if (plan->dense)
-    DISPATCH(launch_dense_decode, P, plan, st);  // every element kept: one positional dequantise stream
+  if (plan->dense)  // every element kept: one positional dequantise stream
+    with_flags(
+        [&](auto r, auto h, auto x) {
+          hipLaunchKernelGGL((k_dense_deq<r.value, h.value, x.value>), dim3(ceil_div(P.n_units, WAVES)), dim3(BLOCK), 0, st,
+                             P);
+        },
+        raw, hb, !plan->decode_latency);
   else
-    DISPATCH(launch_decode_lds, P, plan, st);
-#undef DISPATCH
+    with_flags([&](auto r, auto h, auto hr) { launch_decode_lds<r.value, h.value, hr.value>(P, plan, st); }, raw, hb,
+               plan->high_ratio);
   MARK(2);
-  HIP_CHECK(hipGetLastError());
-  return COALAC_OK;
+  return launched();
 }
 
 int coalac_decode(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
@@ -3821,62 +3733,53 @@ int coalac_ef_accumulate(coalac_plan_t plan, const float* d_in, const float* con
   if ((d_in != nullptr) == (d_seg_in != nullptr))
     return fail(COALAC_EINVAL, "coalac_ef_accumulate: exactly one of d_in and d_seg_in must be given");
   if (!d_resid) return fail(COALAC_EINVAL, "coalac_ef_accumulate: residual pointer is NULL");
-  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_base) | reinterpret_cast<uintptr_t>(d_resid)) & 15)
+  if (addr_bits(d_in, d_base, d_resid) & 15)
     return fail(COALAC_EINVAL, "coalac_ef_accumulate: input/base/residual must be 16-byte aligned");
-  if (plan->n_units == 0) return COALAC_OK;
+  if (plan->proto.n_units == 0) return COALAC_OK;
   int rc = check_device(plan);
   if (rc) return rc;
-  Params P{};
-  fill_meta(P, plan);
+  Params P = plan->proto;
   P.in = d_in;
   P.inptr = d_seg_in;
   P.base = d_base;
   P.out = d_resid;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 g((plan->n_units + WAVES - 1) / WAVES);
-  if (d_base)
-    hipLaunchKernelGGL((k_ef_accumulate<true>), g, dim3(BLOCK), 0, st, P);
-  else
-    hipLaunchKernelGGL((k_ef_accumulate<false>), g, dim3(BLOCK), 0, st, P);
-  HIP_CHECK(hipGetLastError());
-  return COALAC_OK;
+  with_flags(
+      [&](auto hb) {
+        hipLaunchKernelGGL((k_ef_accumulate<hb.value>), dim3(ceil_div(P.n_units, WAVES)), dim3(BLOCK), 0, st, P);
+      },
+      d_base != nullptr);
+  return launched();
 }
 
 int coalac_ef_commit(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
                      const float* d_scale, const uint32_t* d_ustart, float* d_resid, void* stream) {
   if (!plan) return fail(COALAC_EINVAL, "coalac_ef_commit: plan is NULL");
-  if (plan->n_units == 0 || plan->total_k == 0) return COALAC_OK;
+  if (plan->proto.n_units == 0 || plan->total_k == 0) return COALAC_OK;
   if (!d_resid) return fail(COALAC_EINVAL, "coalac_ef_commit: residual pointer is NULL");
   if (!(plan->dense || (d_idx && d_ustart)) || !d_vals)
     return fail(COALAC_EINVAL, "coalac_ef_commit: idx/vals/ustart pointers are NULL (a sparse plan needs the per-unit "
                 "starts the encode wrote)");
   if (plan->bits != 32 && (!d_mn || !d_scale)) return fail(COALAC_EINVAL, "coalac_ef_commit: mn/scale pointers are NULL");
-  if (reinterpret_cast<uintptr_t>(d_resid) & 15)
-    return fail(COALAC_EINVAL, "coalac_ef_commit: residual must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_ef_commit: ustart must be 4-byte aligned");
+  if (addr_bits(d_resid) & 15) return fail(COALAC_EINVAL, "coalac_ef_commit: residual must be 16-byte aligned");
+  if (addr_bits(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_ef_commit: ustart must be 4-byte aligned");
   int rc = check_device(plan);
   if (rc) return rc;
-  Params P{};
-  fill_meta(P, plan);
-  P.cidx = d_idx;
-  P.cvals = d_vals;
-  P.cmn = d_mn;
-  P.cscale = d_scale;
+  Params P = plan->proto;
+  set_payload(P, d_idx, d_vals, d_mn, d_scale);
   P.ustart = d_ustart;
   P.out = d_resid;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 g((plan->n_units + WAVES - 1) / WAVES);
-  const bool raw = plan->bits == 32;
-  if (plan->dense && raw)
-    hipLaunchKernelGGL((k_ef_commit_dense<true>), g, dim3(BLOCK), 0, st, P);
-  else if (plan->dense)
-    hipLaunchKernelGGL((k_ef_commit_dense<false>), g, dim3(BLOCK), 0, st, P);
-  else if (raw)
-    hipLaunchKernelGGL((k_ef_commit<true>), g, dim3(BLOCK), 0, st, P);
-  else
-    hipLaunchKernelGGL((k_ef_commit<false>), g, dim3(BLOCK), 0, st, P);
-  HIP_CHECK(hipGetLastError());
-  return COALAC_OK;
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  with_flags(
+      [&](auto raw) {
+        if (plan->dense)
+          hipLaunchKernelGGL((k_ef_commit_dense<raw.value>), g, dim3(BLOCK), 0, st, P);
+        else
+          hipLaunchKernelGGL((k_ef_commit<raw.value>), g, dim3(BLOCK), 0, st, P);
+      },
+      plan->bits == 32);
+  return launched();
 }
 
 int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, const void* d_vals,
@@ -3885,25 +3788,25 @@ int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, c
                         const uint8_t* d_avg_mask, const float* d_base, float* d_out, void* stream,
                         void* const* events) {
   if (!plan) return fail(COALAC_EINVAL, "coalac_aggregate: plan is NULL");
-  if (clients < 1 || plan->nseg % clients) return fail(COALAC_EINVAL, "coalac_aggregate: %d segments are not %d copies "
-                                                       "of one layout", plan->nseg, clients);
+  const int nseg = (int)plan->proto.nseg;
+  const uint32_t n_units = plan->proto.n_units;
+  if (clients < 1 || nseg % clients)
+    return fail(COALAC_EINVAL, "coalac_aggregate: %d segments are not %d copies of one layout", nseg, clients);
   if (mode != COALAC_AGG_DIV && mode != COALAC_AGG_RECIP && mode != COALAC_AGG_SUM)
     return fail(COALAC_EINVAL, "coalac_aggregate: bad mode %d", mode);
-  if (plan->n_units == 0) return COALAC_OK;
+  if (n_units == 0) return COALAC_OK;
   if (!d_out || !d_weights) return fail(COALAC_EINVAL, "coalac_aggregate: output/weights pointer is NULL");
   if (plan->total_k && (!d_idx || !d_vals || !d_ustart))
     return fail(COALAC_EINVAL, "coalac_aggregate: idx/vals/ustart pointers are NULL (the per-unit starts of wire v2; a "
                 "dense plan's implied indices and starts must be passed here)");
   if (plan->bits != 32 && (!d_mn || !d_scale)) return fail(COALAC_EINVAL, "coalac_aggregate: mn/scale pointers are NULL");
-  if ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_base)) & 15)
-    return fail(COALAC_EINVAL, "coalac_aggregate: output/base must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_ustart) & 3)
-    return fail(COALAC_EINVAL, "coalac_aggregate: ustart must be 4-byte aligned");
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_aggregate: output/base must be 16-byte aligned");
+  if (addr_bits(d_ustart) & 3) return fail(COALAC_EINVAL, "coalac_aggregate: ustart must be 4-byte aligned");
   // the table must be `clients` copies of one layout at constant input / output strides
-  const uint32_t T = (uint32_t)(plan->nseg / clients);
+  const uint32_t T = (uint32_t)(nseg / clients);
   const std::vector<SegDev>& H = plan->hsegs;
-  const uint32_t U0 = plan->n_units / (uint32_t)clients;
-  if (plan->n_units % (uint32_t)clients) return fail(COALAC_EINVAL, "coalac_aggregate: unit count not divisible");
+  const uint32_t U0 = n_units / (uint32_t)clients;
+  if (n_units % (uint32_t)clients) return fail(COALAC_EINVAL, "coalac_aggregate: unit count not divisible");
   const uint64_t S = clients > 1 ? H[T].in_off - H[0].in_off : 0, Kc = clients > 1 ? H[T].out_off - H[0].out_off : 0;
   for (uint32_t c = 1; c < (uint32_t)clients; ++c)
     for (uint32_t t = 0; t < T; ++t) {
@@ -3915,12 +3818,8 @@ int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, c
     }
   int rc = check_device(plan);
   if (rc) return rc;
-  Params P{};
-  fill_meta(P, plan);
-  P.cidx = d_idx;
-  P.cvals = d_vals;
-  P.cmn = d_mn;
-  P.cscale = d_scale;
+  Params P = plan->proto;
+  set_payload(P, d_idx, d_vals, d_mn, d_scale);
   P.base = d_base;
   P.out = d_out;
   AggArgs A{};
@@ -3937,28 +3836,16 @@ int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, c
   const Marks marks{events, 3};
   MARK(0);
   MARK(1);
-  const uint32_t g = (U0 * AGG_SPLIT + WAVES - 1) / WAVES;
-  const bool raw = plan->bits == 32, hb = d_base != nullptr;
-#define AGG(R, H, M) hipLaunchKernelGGL((k_aggregate<R, H, M>), dim3(g), dim3(BLOCK), 0, st, P, A)
-#define AGG_MODES(R, H)                     \
-  do {                                      \
-    if (mode == COALAC_AGG_RECIP)           \
-      AGG(R, H, COALAC_AGG_RECIP);          \
-    else if (mode == COALAC_AGG_SUM)        \
-      AGG(R, H, COALAC_AGG_SUM);            \
-    else                                    \
-      AGG(R, H, COALAC_AGG_DIV);            \
-  } while (0)
-  if (raw) {
-    if (hb) AGG_MODES(true, true); else AGG_MODES(true, false);
-  } else {
-    if (hb) AGG_MODES(false, true); else AGG_MODES(false, false);
-  }
-#undef AGG_MODES
-#undef AGG
+  with_flags(
+      [&](auto raw, auto hb) {
+        with_agg_mode(mode, [&](auto m) {
+          hipLaunchKernelGGL((k_aggregate<raw.value, hb.value, m.value>), dim3(ceil_div(U0 * AGG_SPLIT, WAVES)),
+                             dim3(BLOCK), 0, st, P, A);
+        });
+      },
+      plan->bits == 32, d_base != nullptr);
   MARK(2);
-  HIP_CHECK(hipGetLastError());
-  return COALAC_OK;
+  return launched();
 }
 
 int coalac_aggregate(coalac_plan_t plan, int clients, const int32_t* d_idx, const void* d_vals, const float* d_mn,
@@ -3977,21 +3864,21 @@ int coalac_gather(const void* const* d_src, int n, int elem_bytes, void* d_out, 
   if (n == 0) return COALAC_OK;
   hipLaunchKernelGGL(k_gather, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), d_src,
                      (uint32_t)n, (uint32_t)elem_bytes, d_out);
-  HIP_CHECK(hipGetLastError());
-  return COALAC_OK;
+  return launched();
 }
 
+// The diagnostics read a finished encode's workspace back: the arrays' places come from the same walk as the encode's.
 int coalac_workspace_fallbacks(coalac_plan_t plan, const void* d_ws, void* stream, int* out) {
   if (!plan || !d_ws || !out) return fail(COALAC_EINVAL, "coalac_workspace_fallbacks: NULL argument");
   *out = 0;
-  if (plan->nseg == 0 || plan->dense) return COALAC_OK;
-  std::vector<uint32_t> st(plan->nseg);
-  std::vector<uint32_t> large(plan->n_large);
+  if (plan->proto.nseg == 0 || plan->dense) return COALAC_OK;
+  Params W = plan->proto;
+  carve_workspace(W, false, const_cast<void*>(d_ws));
+  std::vector<uint32_t> st(W.nseg);
+  std::vector<uint32_t> large(W.n_large);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_CHECK(hipMemcpyAsync(st.data(), static_cast<const uint8_t*>(d_ws) + plan->ws.status, 4 * st.size(),
-                           hipMemcpyDeviceToHost, s));
-  if (plan->n_large)
-    HIP_CHECK(hipMemcpyAsync(large.data(), plan->large_list, 4 * large.size(), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(st.data(), W.status, 4 * st.size(), hipMemcpyDeviceToHost, s));
+  if (W.n_large) HIP_CHECK(hipMemcpyAsync(large.data(), W.large_list, 4 * large.size(), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   int c = 0;
   for (uint32_t s2 : large) c += st[s2] == 1;
@@ -4003,11 +3890,13 @@ int coalac_debug_brackets(coalac_plan_t plan, const void* d_ws, void* stream, ui
                           int n) {
   if (!plan || !d_ws || !host_tlo || !host_thi || n < 0) return fail(COALAC_EINVAL, "coalac_debug_brackets: bad argument");
   if (plan->dense) return 0;
-  const size_t cnt = std::min<size_t>((size_t)n, plan->n_lunits);
+  Params W = plan->proto;
+  carve_workspace(W, false, const_cast<void*>(d_ws));
+  const size_t cnt = std::min<size_t>((size_t)n, W.n_lunits);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (cnt) {
-    HIP_CHECK(hipMemcpyAsync(host_tlo, static_cast<const uint8_t*>(d_ws) + plan->ws.tlo, 4 * cnt, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(host_thi, static_cast<const uint8_t*>(d_ws) + plan->ws.thi, 4 * cnt, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(host_tlo, W.tlo, 4 * cnt, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(host_thi, W.thi, 4 * cnt, hipMemcpyDeviceToHost, s));
   }
   HIP_CHECK(hipStreamSynchronize(s));
   return (int)cnt;
@@ -4015,11 +3904,13 @@ int coalac_debug_brackets(coalac_plan_t plan, const void* d_ws, void* stream, ui
 
 int coalac_debug_stamps(coalac_plan_t plan, const void* d_ws, void* stream, uint64_t* host, int n) {
   if (!plan || !d_ws || !host || n < 0) return fail(COALAC_EINVAL, "coalac_debug_stamps: bad argument");
-  const size_t cap = (size_t)NSTAMP * std::max<size_t>(plan->nseg, 1);
+  if (plan->dense) return 0;  // (a dense plan's workspace has no stamp rows)
+  Params W = plan->proto;
+  carve_workspace(W, false, const_cast<void*>(d_ws));
+  const size_t cap = (size_t)NSTAMP * std::max<size_t>(W.nseg, 1);
   const size_t cnt = std::min<size_t>((size_t)n, cap);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_CHECK(hipMemcpyAsync(host, static_cast<const uint8_t*>(d_ws) + plan->ws.stamps, 8 * cnt,
-                           hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(host, W.stamps, 8 * cnt, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   return (int)cnt;
 }

@@ -55,7 +55,7 @@ def test_null_arguments():
     assert lib.coalac_plan_create(None, 1, 8, None) == -1
     assert lib.coalac_plan_destroy(None) == 0
     assert lib.coalac_encode(None, None, None, None, None, None, None, None, None, 0, 0, None) == -1
-    assert lib.coalac_decode(None, None, None, None, None, None, None, None, None, 0, None) == -1
+    assert lib.coalac_decode(None, None, None, None, None, None, None, None, None) == -1
 
 
 def test_binding_argument_counts_match_header():
