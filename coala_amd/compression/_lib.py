@@ -45,6 +45,11 @@ SIGNATURES = [
     # error feedback: plan, in, seg pointers, base, resid, stream / plan, idx, vals, mn, scale, ustart, resid, stream
     ("coalac_ef_accumulate", _I, [_P, _P, _P, _P, _P, _P]),
     ("coalac_ef_commit", _I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    # compact payload: plan, bytes / plan, idx, vals, packed, packed_bytes, stream / plan, packed, packed_bytes, ustart,
+    # idx, vals, stream
+    ("coalac_plan_packed_bytes", _I, [_P, ctypes.POINTER(_U64)]),
+    ("coalac_pack", _I, [_P, _P, _P, _P, _U64, _P]),
+    ("coalac_unpack", _I, [_P, _P, _U64, _P, _P, _P, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -56,7 +61,7 @@ SIGNATURES = [
     ("coalac_debug_brackets", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _I]),
 ]
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class CodecError(RuntimeError):

@@ -357,7 +357,8 @@ def _to_host(*ts):
     return out
 
 
-_NP_DTYPES = {torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8, torch.int64: np.int64}
+_NP_DTYPES = {torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8, torch.int64: np.int64,
+              torch.uint32: np.uint32}
 # the dtypes a passthrough entry of a blob may name (a state_dict's non-fp32 or empty entries); a blob naming
 # anything else is rejected rather than handed to getattr(torch, ...)
 _RAW_DTYPES = {_dtype_name(d): d for d in (torch.float32, torch.float64, torch.float16, torch.bfloat16, torch.int64,
@@ -525,13 +526,17 @@ class CompressedUpdate:
     """Picklable carrier of one compressed client update (what `compression()` leaves in self.model).
 
     Holds the encoded buffers (device tensors right after encode; CPU tensors after unpickling) and the
-    raw passthrough entries. Pickles to the COALAQ1 blob (wire.py).
+    raw passthrough entries. Pickles to the COALAQ1 blob (wire.py). A compact carrier (header "compact": wire
+    v3) also holds the packed entry stream, `packed`, and ships that instead of idx and the uint8 codes.
     """
 
-    def __init__(self, header, encoded, raw, blob=None):
+    def __init__(self, header, encoded, raw, blob=None, packed=None):
         self.header = header
         self.encoded = encoded
         self.raw = raw
+        # a compact carrier's packed entry stream (uint32[P]): the device buffer the encode packed, or None until
+        # first asked for (encoded buffers on the CPU, or a backend without pack); shared by every deep copy
+        self._packed = [packed]
         # the packed COALAQ1 bytes, built on first pickle and shared by every deep copy: the reference
         # pickles copy.deepcopy(self.model) (client/base.py:363), so the payload is packed once
         self._blob = [blob]
@@ -544,8 +549,20 @@ class CompressedUpdate:
         other.encoded = self.encoded
         other.raw = self.raw
         other._blob = self._blob
+        other._packed = self._packed
         memo[id(self)] = other
         return other
+
+    @property
+    def packed(self):
+        """A compact carrier's packed entry stream (wire.py, version 3) as a uint32 tensor, else None. Packed on the
+        GPU right after the encode where the plan can (CodecPlan.pack); otherwise on the host, on first use."""
+        if not self.header.get("compact"):
+            return None
+        if self._packed[0] is None:
+            idx, vals = _to_host(self.encoded.idx, self.encoded.vals)
+            self._packed[0] = torch.from_numpy(wire.pack_entries(idx, vals, self.header["bits"]))
+        return self._packed[0]
 
     # -- size accounting (client/base.py:155, 474-487) -------------------------------------------
     @property
@@ -555,6 +572,9 @@ class CompressedUpdate:
         ib = 0 if h["ratio"] >= 1.0 else 4  # ratio 1: indices implied, not shipped (wire.py "dense")
         raw_b = self.raw.nbytes if isinstance(self.raw, RawState) else \
             sum(t.numel() * t.element_size() for t in self.raw.values())
+        if h.get("compact"):  # the packed stream, and the values only as fp32
+            return (8 * h["n_segments"] + 4 * wire.packed_words(h["total_k"], h["bits"])
+                    + (4 * h["total_k"] if h["bits"] == RAW_BITS else 0) + 4 * h["n_units"] + raw_b)
         return 8 * h["n_segments"] + (ib + vb) * h["total_k"] + 4 * h.get("n_units", 0) + raw_b
 
     def parameters(self):
@@ -577,7 +597,7 @@ class CompressedUpdate:
         # the header (with each raw entry's blob offset) depends on the layout and the raw byte counts only
         sizes = tuple(len(rawb[n]) for n in rawb)
         key = (id(h["entries"]), h["ratio"], h["bits"], h["mode"], h["n_segments"], h.get("total_k"),
-               h.get("n_units"), sizes)
+               h.get("n_units"), sizes, bool(h.get("compact")))
         hit = _PACKED_HEADERS.get(key)
         if hit is not None and hit[0] is h["entries"]:
             hjson = hit[1]
@@ -598,23 +618,31 @@ class CompressedUpdate:
                 while len(_PACKED_HEADERS) > 16:
                     _PACKED_HEADERS.popitem(last=False)
         enc = self.encoded
+        rawbytes = b"".join(rawb[e["name"]] for e in h["entries"] if e["kind"] == "raw")
+        if h.get("compact"):  # wire v3: the packed stream instead of idx and the uint8 codes, neither copied
+            f32 = h["bits"] == RAW_BITS
+            arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device), enc.ustart, *((enc.vals,) if f32 else ()))
+            return wire.pack({"compact": True, "n_units": h["n_units"]}, arrs[0], arrs[1], None,
+                             arrs[4] if f32 else None, rawbytes, header_json=hjson, ustart=arrs[3], packed=arrs[2])
         v2 = "n_units" in h  # wire v2: the per-unit starts ride along
         arrs = _to_host(enc.mn, enc.scale, enc.idx, enc.vals, *((enc.ustart,) if v2 else ()))
         pack_h = {"dense": h["ratio"] >= 1.0}
         if v2:
             pack_h["n_units"] = h["n_units"]
-        return wire.pack(pack_h, *arrs[:4], b"".join(rawb[e["name"]] for e in h["entries"] if e["kind"] == "raw"),
-                         header_json=hjson, ustart=arrs[4] if v2 else None)
+        return wire.pack(pack_h, *arrs[:4], rawbytes, header_json=hjson, ustart=arrs[4] if v2 else None)
 
-    def encoded_to(self, device, staging=None):
+    def encoded_to(self, device, staging=None, plan=None):
         """The encoded buffers on `device`. An unpickled update (the server side of a remote upload,
         coala/server/service.py:81-111) is moved with ONE host-to-device copy of the blob's mn / scale /
         idx / vals region through `staging` (a pinned host buffer: staging(nbytes) -> uint8 tensor), so
-        the copy is asynchronous on the caller's stream; device tensors are typed views into it."""
+        the copy is asynchronous on the caller's stream; device tensors are typed views into it. A compact
+        blob's region (mn ... ustart) holds the packed stream: idx / vals are then materialised on the device by
+        `plan`.unpack (the decoding plan of this update; without one, the host-unpacked buffers are copied)."""
         device = torch.device(device)
         blob = self._blob[0]
+        compact = bool(self.header.get("compact"))
         if (staging is None or device.type != "cuda" or blob is None or self.header.get("dense")
-                or self.encoded.idx.device == device):
+                or self.encoded.idx.device == device or (compact and getattr(plan, "unpack", None) is None)):
             return self.encoded.to(device, non_blocking=True)
         _, sec = wire.sections(blob, self.header)
         lo = sec["mn"][0]
@@ -622,13 +650,22 @@ class CompressedUpdate:
         hi = last[0] + last[1]
         stage = staging(hi - lo)
         stage[:hi - lo].numpy()[:] = np.frombuffer(blob, dtype=np.uint8, count=hi - lo, offset=lo)
-        dev = torch.empty(hi - lo, dtype=torch.uint8, device=device)
-        dev.copy_(stage[:hi - lo], non_blocking=True)
-        vdt = torch.float32 if self.header["bits"] == RAW_BITS else torch.uint8
+        K = int(self.header["total_k"])
+        room = (hi - lo + 15) // 16 * 16  # a compact blob: idx (and the uint8 codes) are unpacked behind the region
+        f32 = self.header["bits"] == RAW_BITS
+        dev = torch.empty(room + (4 * K + (0 if f32 else K) if compact else 0), dtype=torch.uint8, device=device)
+        dev[:hi - lo].copy_(stage[:hi - lo], non_blocking=True)
+        vdt = torch.float32 if f32 else torch.uint8
 
         def view(name, dt):
             o, n = sec[name]
             return dev[o - lo:o - lo + n].view(dt)
+        if compact:
+            idx = dev[room:room + 4 * K].view(torch.int32)
+            vals = view("vals", vdt) if f32 else dev[room + 4 * K:room + 5 * K]
+            ustart = view("ustart", torch.int32)
+            plan.unpack(view("packed", torch.uint32), ustart, out=(idx, vals))
+            return Encoded(idx, vals, view("mn", torch.float32), view("scale", torch.float32), ustart)
         return Encoded(view("idx", torch.int32), view("vals", vdt), view("mn", torch.float32),
                        view("scale", torch.float32), view("ustart", torch.int32) if "ustart" in sec else None)
 
@@ -676,6 +713,15 @@ def _dense_elements(entries):
             while len(_DENSE) > 32:
                 _DENSE.popitem(last=False)
     return hit[1]
+
+
+def _all_kept(plan):
+    """Every segment of the plan keeps all its elements (the library's dense codec: nothing to pack)."""
+    dense = getattr(plan, "dense", None)
+    if dense is None:
+        segs = plan.table.segs
+        dense = bool(len(segs)) and bool((segs[:, 1] == segs[:, 2]).all())
+    return dense
 
 
 _VALIDATED = OrderedDict()  # (id(entries), ratio, n_segments, total_k) -> (entries, ns_rep, first, units) of a layout
@@ -765,9 +811,13 @@ class UpdateCodec:
         recycle: decode_module / aggregate decode into a module this codec returned earlier once nothing
                outside the codec references it (_TreeRecipe.idle_skeleton); False builds a new module
                every call. release_pool() drops every pooled module.
+        compact: sparse uploads travel in the compact payload format (wire v3): every kept entry as one
+               (12 + bits)-bit field instead of an int32 index and a whole uint8 code — 2.5 bytes per entry at 8 bits,
+               2 at 4 bits, instead of 5. Lossless (the decoded result is bit-identical) and self-describing (a decoder
+               needs no switch). A dense plan or ratio 1 keeps the dense format. Off by default.
     """
 
-    def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True):
+    def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True, compact=False):
         if not (0.0 < float(ratio) <= 1.0):
             raise ValueError(f"ratio must be in (0, 1], got {ratio}")
         if bits not in VALID_BITS:
@@ -776,6 +826,7 @@ class UpdateCodec:
             raise ValueError(f"mode must be one of {MODES}, got {mode}")
         self.ratio, self.bits, self.mode = float(ratio), int(bits), mode
         self.recycle = bool(recycle)
+        self.compact = bool(compact)
         self.backend = backend if backend is not None else HipBackend()
         self._plans = {}
         self._plan_fast = OrderedDict()  # (id(sizes), ratio, bits, clients) -> (sizes, device, plan)
@@ -927,7 +978,15 @@ class UpdateCodec:
         header["total_k"] = int(plan.table.total_k)
         if enc.ustart is not None and self.ratio < 1.0:  # wire v2 (a dense download implies its starts)
             header["n_units"] = int(plan.table.n_units)
-        return CompressedUpdate(header, enc, raw() if callable(raw) else raw)
+        packed = None
+        if self.compact and "n_units" in header and not _all_kept(plan):
+            # wire v3: the entries repacked on the encode's stream, directly after it (a plan without pack — the test
+            # backends — or buffers on the CPU: the carrier packs on the host when it is pickled)
+            header["compact"] = True
+            pack = getattr(plan, "pack", None)
+            if pack is not None and enc.idx.device.type == "cuda":
+                packed = pack(enc, stream=cur)
+        return CompressedUpdate(header, enc, raw() if callable(raw) else raw, packed=packed)
 
     def _thread_stream(self, device):
         """One HIP stream per (thread, device): concurrent decodes from several threads overlap on the GPU
@@ -1042,7 +1101,7 @@ class UpdateCodec:
                 # (the caller's stream's pool)
                 out = into.flat if into is not None else torch.empty(plan.span, dtype=torch.float32, device=device)
                 with torch.cuda.stream(side):
-                    enc = update.encoded_to(device, staging=self._staging)
+                    enc = update.encoded_to(device, staging=self._staging, plan=plan)
                     self._staged(side)
                     flat = plan.decode(enc, base=base_flat, out=out, stream=side)
                     if into is not None:
@@ -1128,8 +1187,9 @@ class UpdateCodec:
         h0 = updates[0].header
         for u in updates[1:]:
             h = u.header
-            if (h["ratio"], h["bits"], h["mode"], h["entries"]) != (h0["ratio"], h0["bits"], h0["mode"], h0["entries"]):
-                raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode")
+            if (h["ratio"], h["bits"], h["mode"], h["entries"], bool(h.get("compact"))) != \
+                    (h0["ratio"], h0["bits"], h0["mode"], h0["entries"], bool(h0.get("compact"))):
+                raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode / payload format")
         sizes = [e["n"] for e in h0["entries"] if e["kind"] == "seg"]
         device = self.backend.default_device() if device is None else torch.device(device)
         base_flat = None

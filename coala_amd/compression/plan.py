@@ -316,6 +316,69 @@ class CodecPlan:
         _lib.check(rc, "coalac_ef_commit")
         return resid
 
+    # -- compact payload (wire v3) ----------------------------------------------------------------
+    @property
+    def packed_words(self):
+        """uint32 words of the plan's packed entry stream: ceil(total_k * (12 + code bits) / 32) (wire.py)."""
+        n = self.__dict__.get("_packed_words")
+        if n is None:
+            b = ctypes.c_uint64()
+            _lib.check(self._lib.coalac_plan_packed_bytes(self._h, ctypes.byref(b)), "coalac_plan_packed_bytes")
+            n = self._packed_words = b.value // 4
+        return n
+
+    def _check_packed(self, t, name):
+        if t.device != self.device or t.dtype != torch.uint32 or not t.is_contiguous() or t.numel() < self.packed_words:
+            raise ValueError(f"{name}: need a contiguous uint32[{self.packed_words}] tensor on {self.device}, got "
+                             f"{t.dtype}[{t.numel()}] on {t.device}")
+
+    def pack(self, enc, out=None, stream=None):
+        """enc.idx / enc.vals -> the packed entry stream, uint32[packed_words] (coalac_pack: one (12 + code bits)-bit
+        field per entry position; at bits 32 the values are not read). Asynchronous on `stream`; a dense plan has
+        nothing to pack (ValueError)."""
+        if self.dense:
+            raise ValueError("pack: a dense plan's indices are implied, there is nothing to pack")
+        self._check_encoded(enc)
+        if enc.idx.numel() < self.total_k:
+            raise ValueError(f"pack: idx holds {enc.idx.numel()} entries, the plan has {self.total_k}")
+        if enc.idx.data_ptr() % 16 or enc.vals.data_ptr() % 16:
+            raise ValueError("pack: idx / vals storage must be 16-byte aligned")
+        with _on(stream):
+            if out is None:
+                out = torch.empty(self.packed_words, dtype=torch.uint32, device=self.device)
+        self._check_packed(out, "packed output")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_pack(self._h, _ptr(enc.idx), _ptr(enc.vals), _ptr(out),
+                                       ctypes.c_uint64(4 * out.numel()), _stream_handle(stream))
+        _lib.check(rc, "coalac_pack")
+        return out
+
+    def unpack(self, packed, ustart, out=None, stream=None):
+        """The packed entry stream + the per-unit starts -> (idx int32[total_k], vals) (coalac_unpack). out: an
+        (idx, vals) pair to write into — only the positions of the plan's own segments are written; at bits 32 vals
+        is not written (the fp32 values travel in their own section). Asynchronous on `stream`."""
+        if self.dense:
+            raise ValueError("unpack: a dense plan's indices are implied, there is nothing to unpack")
+        self._check_packed(packed, "packed stream")
+        if ustart.device != self.device or ustart.dtype != torch.int32 or not ustart.is_contiguous() or \
+                ustart.numel() != self.n_units:
+            raise ValueError(f"unpack: need the plan's {self.n_units} per-unit starts as a contiguous int32 tensor on "
+                             f"{self.device}, got {ustart.dtype}[{ustart.numel()}] on {ustart.device}")
+        with _on(stream):
+            if out is None:
+                out = (torch.empty(self.total_k, dtype=torch.int32, device=self.device),
+                       torch.empty(self.total_k, dtype=self.vals_dtype, device=self.device))
+        idx, vals = out
+        for t, dt in ((idx, torch.int32), (vals, self.vals_dtype)):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or t.numel() < self.total_k:
+                raise ValueError(f"unpack output: need {dt}[{self.total_k}] on {self.device}, got "
+                                 f"{t.dtype}[{t.numel()}] on {t.device}")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_unpack(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(ustart),
+                                         _ptr(idx), _ptr(vals), _stream_handle(stream))
+        _lib.check(rc, "coalac_unpack")
+        return idx, vals
+
     def unit_starts(self, idx, stream=None):
         """The per-unit starts (wire v2) of this plan's idx list, computed on the device for a payload that carries
         none (a version-1 blob, or an Encoded built without them): for unit j of segment s, the number of the

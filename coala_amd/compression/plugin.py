@@ -29,6 +29,9 @@ Behaviour:
   * error feedback (opt-in, `codec_error_feedback = True`, delta mode): compression() adds the client's residual —
     what its earlier uploads dropped — to the update before the top-k and keeps what this upload drops
     (reset_error_feedback() zeroes it). The upload is an ordinary delta-mode carrier; the server is unchanged.
+  * compact payload (opt-in, `codec_compact = True` on the client): a sparse upload ships every kept entry as one
+    (12 + bits)-bit field (wire v3) instead of 5 bytes; the blob describes itself, so the server needs
+    no switch and decodes it to the same bits. Uploads of mixed formats are decoded one by one, not fused.
   * calculate_model_size(): reports the real payload size for a carrier (base.py:155, 474-487).
   * server decompression(model): CompressedUpdate -> a NEW nn.Module (never aliases self.model, which
     aggregation overwrites, base.py:571) built on the pre-aggregation global model (delta mode: w_global
@@ -101,7 +104,7 @@ class _CodecOwner:
         c = self.__dict__.get("_update_codec")
         if c is None:
             c = UpdateCodec(self.codec_ratio, self.codec_bits, self.codec_mode, self.codec_backend,
-                            recycle=self.codec_recycle)
+                            recycle=self.codec_recycle, compact=getattr(self, "codec_compact", False))
             self.__dict__["_update_codec"] = c
         return c
 
@@ -117,6 +120,11 @@ class CompressionClientMixin(_CodecOwner):
     # encode device (4 bytes per fp32 parameter per client) and is added to the next round's update, so nothing is
     # lost, only delayed (EF-SGD). Off by default: uploads are then exactly what they were.
     codec_error_feedback = False
+
+    # compact payload for sparse uploads (wire v3): every kept entry as one (12 + codec_bits)-bit field
+    # instead of an int32 index and a uint8 code. Lossless; the blob describes itself, so the server has no switch.
+    # Off by default: blobs and sizes are then exactly what they were.
+    codec_compact = False
 
     def reset_error_feedback(self):
         """Zero this client's residual (e.g. when it joins a new task with the same model)."""
@@ -345,7 +353,8 @@ class CompressionServerMixin(_CodecOwner):
                 weights = [1 for _ in models]
             h0 = models[0].header
             if all(m.header["entries"] == h0["entries"] and
-                   (m.header["ratio"], m.header["bits"], m.header["mode"]) == (h0["ratio"], h0["bits"], h0["mode"])
+                   (m.header["ratio"], m.header["bits"], m.header["mode"], bool(m.header.get("compact"))) ==
+                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")))
                    for m in models):
                 base = self._global_snapshot() if h0["mode"] == "delta" else None
                 codec = self._codec()

@@ -7,7 +7,7 @@ self-describing because remote clients never receive new config keys (OperateCon
 
 Layout (little-endian):
     0   8B   magic b"COALAQ1\\0"
-    8   u32  format version (2 when the header has "n_units", else 1)
+    8   u32  format version (3 when the header has "compact", 2 when it has "n_units" only, else 1)
     12  u32  header length H
     16  H    UTF-8 JSON header: ratio, bits, mode, n_segments, total_k, [n_units], entries[]
              entry = {"name", "dtype", "shape", "kind": "seg", "seg": i, "n", "k", "out_off"}
@@ -21,6 +21,22 @@ Layout (little-endian):
     carries an empty idx section, and unpack returns an empty idx: the indices stay implied all the way into
     the GPU's dense decode (coalac.hip k_dense_deq), never materialised. This is the download-direction
     default (dense 8-bit weights, ~4x smaller than fp32 instead of 5 B per element with explicit indices).
+
+Version 3, the COMPACT payload (opt-in, sparse uploads only; header key "compact": true, "n_units" mandatory):
+         mn f32[T] | scale f32[T] | packed u32[P] | [vals f32[K] only when bits == 32] | ustart i32[U] | raw bytes
+    For K = total_k entry positions and code width b (b = bits when bits <= 8; b = 0 when bits == 32, whose fp32
+    values stay in their own section), every entry is one field of w = 12 + b bits (12 <= w <= 20):
+        field_j = (idx[j] & 0xFFF) | (code_j << 12)          j: the position in the idx / vals arrays
+    The packed section is a little-endian bit stream of uint32 words: field j occupies bits [j*w, (j+1)*w), bit t
+    of the stream is bit t % 32 of word t // 32. It is P = ceil(K*w / 32) words long and all padding bits are zero,
+    so equal payloads give equal bytes. Only the low 12 bits of an index travel: the upper bits are the number of
+    its 4096-element unit, which ustart already says. Unit u of segment s, the u_s-th unit of that segment, owns
+    the segment-relative entries [ustart[u], ustart[u+1]) (the segment's last unit ends at k_s), clamped to
+    [0, k_s] with begin <= end (and to at most the unit's element count: a unit keeps no more entries than it has
+    elements), exactly as the decode kernels clamp. For each owned entry e: j = out_off_s + e,
+        idx[j] = (u_s << 12) | (field_j & 0xFFF)      vals[j] = field_j >> 12
+    pack_entries / unpack_entries below are this format on the host (numpy); the GPU's k_pack / k_unpack
+    (coalac.hip) produce and read the same bytes.
 """
 import json
 import struct
@@ -29,28 +45,108 @@ from collections import OrderedDict
 
 import numpy as np
 
+from .spec import RAW_BITS, UNIT, VALID_BITS, k_for
+
 MAGIC = b"COALAQ1\0"
 VERSION = 1     # mn | scale | idx | vals | raw
 VERSION_2 = 2   # ... | vals | ustart | raw
+VERSION_3 = 3   # mn | scale | packed | [vals f32] | ustart | raw  (header "compact": true)
+INDEX_BITS = 12  # low index bits in a packed field: log2(UNIT), the position inside the entry's 4096-element unit
 
 
 def _pad16(n):
     return (16 - n % 16) % 16
 
 
-def pack(header, mn, scale, idx, vals, raw, header_json=None, ustart=None):
+def packed_words(total_k, bits):
+    """uint32 words of the packed entry stream of total_k entries: ceil(total_k * (12 + code bits) / 32)."""
+    return (int(total_k) * field_bits(bits) + 31) // 32
+
+
+def field_bits(bits):
+    """Width w of a packed field: 12 index bits + the code (none at bits 32, whose values are not packed)."""
+    return INDEX_BITS + (0 if int(bits) == RAW_BITS else int(bits))
+
+
+def pack_entries(idx, vals, bits):
+    """idx int32[K], vals (uint8[K] codes; ignored at bits 32) -> the packed stream, uint32[ceil(K*w/32)]: field j =
+    (idx[j] & 0xFFF) | (code_j << 12) at bits [j*w, (j+1)*w) of a little-endian bit stream, padding bits zero."""
+    w = field_bits(bits)
+    f = np.asarray(idx).astype(np.uint32) & np.uint32(UNIT - 1)
+    if w > INDEX_BITS:
+        f |= (np.asarray(vals).astype(np.uint32) & np.uint32((1 << (w - INDEX_BITS)) - 1)) << np.uint32(INDEX_BITS)
+    K = f.size
+    stream = np.zeros(packed_words(K, bits) * 32, dtype=np.uint8)
+    stream[:K * w] = ((f[:, None] >> np.arange(w, dtype=np.uint32)) & np.uint32(1)).astype(np.uint8).reshape(-1)
+    return np.packbits(stream, bitorder="little").view("<u4")
+
+
+def unpack_entries(packed, ustart, segs_n, segs_k, bits):
+    """The packed stream + per-unit starts -> (idx int32[K], vals uint8[K]) for segments of segs_n elements keeping
+    segs_k entries each, laid out back to back (out_off = the running sum of k), K = sum(segs_k). The ranges the
+    starts give are clamped as the kernels clamp them, so any starts reconstruct in range; positions no unit owns
+    stay 0 (never with a valid payload). At bits 32 vals is all zero (the fp32 values are their own section)."""
+    w = field_bits(bits)
+    n = np.asarray(segs_n, dtype=np.int64).reshape(-1)
+    k = np.asarray(segs_k, dtype=np.int64).reshape(-1)
+    if n.size != k.size or np.any(n < 0) or np.any(k < 0) or np.any(k > n):
+        raise ValueError("COALAQ1: bad segment sizes for a packed stream")
+    K = int(k.sum())
+    packed = np.ascontiguousarray(packed, dtype="<u4")
+    if packed.size < packed_words(K, bits):
+        raise ValueError("COALAQ1: truncated packed section")
+    nu = (n + UNIT - 1) // UNIT
+    ustart = np.asarray(ustart).astype(np.uint32).astype(np.int64)  # (the kernels read the starts as unsigned)
+    if ustart.size != int(nu.sum()):
+        raise ValueError("COALAQ1: per-unit start count mismatch")
+    # every field: the one or two words that hold it, as one 64-bit value
+    bit = np.arange(K, dtype=np.int64) * w
+    wd, sh = bit >> 5, (bit & 31).astype(np.uint64)
+    words = np.concatenate([packed[:packed_words(K, bits)], np.zeros(1, dtype="<u4")]).astype(np.uint64)
+    f = (((words[wd] | (words[wd + 1] << np.uint64(32))) >> sh) & np.uint64((1 << w) - 1)).astype(np.uint32)
+    # every unit: its segment, its number inside the segment, its clamped entry range
+    seg = np.repeat(np.arange(n.size), nu)
+    first_unit = np.cumsum(nu) - nu
+    u_s = np.arange(ustart.size, dtype=np.int64) - first_unit[seg]
+    ks = k[seg]
+    last = u_s == nu[seg] - 1
+    ulen = np.minimum(UNIT, n[seg] - u_s * UNIT)
+    lo = np.minimum(ustart, ks)
+    nxt = np.append(ustart[1:], 0)
+    hi = np.maximum(lo, np.minimum(np.minimum(np.where(last, ks, nxt), ks), lo + ulen))
+    cnt = hi - lo
+    out_off = (np.cumsum(k) - k)[seg]
+    owned = int(cnt.sum())
+    j = np.repeat(out_off + lo - (np.cumsum(cnt) - cnt), cnt) + np.arange(owned, dtype=np.int64)
+    idx = np.zeros(K, dtype=np.int32)
+    vals = np.zeros(K, dtype=np.uint8)
+    idx[j] = ((np.repeat(u_s, cnt) << INDEX_BITS) | (f[j] & np.uint32(UNIT - 1))).astype(np.int32)
+    vals[j] = (f[j] >> np.uint32(INDEX_BITS)).astype(np.uint8)
+    return idx, vals
+
+
+def pack(header, mn, scale, idx, vals, raw, header_json=None, ustart=None, packed=None):
     """numpy arrays + raw bytes -> blob (bytes). A "dense" header drops idx (it is implied). header_json: the
     header's JSON encoding, if the caller has it already. ustart: the per-unit starts (version 2; the header
-    must then carry "n_units" = len(ustart))."""
+    must then carry "n_units" = len(ustart)). packed: the packed entry stream (version 3, which needs ustart and a
+    header with "compact": true): it stands where idx stood, and vals is the fp32 values at bits 32, else None."""
     if header.get("dense"):
         idx = np.zeros(0, dtype=np.int32)
     if (ustart is not None) != ("n_units" in header) or (ustart is not None and len(ustart) != header["n_units"]):
         raise ValueError("COALAQ1: ustart section and header n_units disagree")
+    if (packed is not None) != bool(header.get("compact")) or (packed is not None and ustart is None):
+        raise ValueError("COALAQ1: a compact payload needs the packed stream, the per-unit starts and \"compact\"")
     h = header_json if header_json is not None else encode_header(header)
-    parts = [MAGIC, struct.pack("<II", VERSION if ustart is None else VERSION_2, len(h)), h]
+    ver = VERSION_3 if packed is not None else VERSION if ustart is None else VERSION_2
+    parts = [MAGIC, struct.pack("<II", ver, len(h)), h]
     size = 16 + len(h)
-    arrays = [np.ascontiguousarray(mn, "<f4"), np.ascontiguousarray(scale, "<f4"),
-              np.ascontiguousarray(idx, "<i4"), np.ascontiguousarray(vals)]
+    arrays = [np.ascontiguousarray(mn, "<f4"), np.ascontiguousarray(scale, "<f4")]
+    if packed is not None:
+        arrays.append(np.ascontiguousarray(packed, "<u4"))
+        if vals is not None:
+            arrays.append(np.ascontiguousarray(vals, "<f4"))
+    else:
+        arrays += [np.ascontiguousarray(idx, "<i4"), np.ascontiguousarray(vals)]
     if ustart is not None:
         arrays.append(np.ascontiguousarray(ustart, "<i4"))
     for arr in arrays:
@@ -100,10 +196,16 @@ def sections(blob, header=None):
     if header is None:
         header = _parse_header(mv, hl)
     T, K = int(header["n_segments"]), int(header["total_k"])
-    vsz = 4 if int(header["bits"]) == 32 else 1
+    bits = int(header["bits"])
+    vsz = 4 if bits == RAW_BITS else 1
     pos = 16 + hl
     out = {}
-    names = [("mn", 4 * T), ("scale", 4 * T), ("idx", 0 if header.get("dense") else 4 * K), ("vals", vsz * K)]
+    if header.get("compact"):  # version 3: the packed stream where idx stood; the values only as fp32
+        names = [("mn", 4 * T), ("scale", 4 * T), ("packed", 4 * packed_words(K, bits))]
+        if bits == RAW_BITS:
+            names.append(("vals", 4 * K))
+    else:
+        names = [("mn", 4 * T), ("scale", 4 * T), ("idx", 0 if header.get("dense") else 4 * K), ("vals", vsz * K)]
     if "n_units" in header:
         names.append(("ustart", 4 * int(header["n_units"])))
     for name, n in names:
@@ -115,23 +217,34 @@ def sections(blob, header=None):
 
 def unpack(blob):
     """blob -> (header dict, mn, scale, idx, vals, raw bytes, ustart or None). Arrays are read-only views of
-    blob; a "dense" blob's idx is empty (implied)."""
+    blob; a "dense" blob's idx is empty (implied). A compact (version 3) blob's idx and uint8 vals are rebuilt
+    from its packed stream (unpack_entries, with every segment's k = k_for(n, ratio) as validate() expects)."""
     mv = memoryview(blob)
     if bytes(mv[:8]) != MAGIC:
         raise ValueError("not a COALAQ1 blob (bad magic)")
     ver, hl = struct.unpack_from("<II", mv, 8)
-    if ver not in (VERSION, VERSION_2):
+    if ver not in (VERSION, VERSION_2, VERSION_3):
         raise ValueError(f"unsupported COALAQ1 version {ver}")
     header = _parse_header(mv, hl)
-    if (ver == VERSION_2) != ("n_units" in header):
+    compact = ver == VERSION_3
+    if compact != bool(header.get("compact")):
+        raise ValueError("COALAQ1: version and header compact disagree")
+    if (ver in (VERSION_2, VERSION_3)) != ("n_units" in header):
         raise ValueError("COALAQ1: version and header n_units disagree")
     T, K = int(header["n_segments"]), int(header["total_k"])
-    vdt = np.dtype("<f4") if int(header["bits"]) == 32 else np.dtype("u1")
+    bits = int(header["bits"])
+    vdt = np.dtype("<f4") if bits == RAW_BITS else np.dtype("u1")
     pos = 16 + hl
     out = []
     dense = bool(header.get("dense"))
-    layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<i4"), 0 if dense else K), (vdt, K)]
-    if ver == VERSION_2:
+    if compact:
+        if dense or bits not in VALID_BITS or K < 0:
+            raise ValueError("COALAQ1: bad compact header")
+        layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<u4"), packed_words(K, bits)),
+                  (vdt, K if bits == RAW_BITS else 0)]
+    else:
+        layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<i4"), 0 if dense else K), (vdt, K)]
+    if ver != VERSION:
         layout.append((np.dtype("<i4"), int(header["n_units"])))
     for dt, n in layout:
         pos += _pad16(pos)
@@ -143,5 +256,12 @@ def unpack(blob):
     raw = bytes(mv[pos:])
     if dense and K != sum(int(e["n"]) for e in header["entries"] if e["kind"] == "seg"):
         raise ValueError("COALAQ1: dense header with k != n")
-    ustart = out[4] if ver == VERSION_2 else None
+    ustart = out[4] if ver != VERSION else None
+    if compact:
+        ns = [int(e["n"]) for e in header["entries"] if e["kind"] == "seg"]
+        ks = [k_for(n, float(header["ratio"])) for n in ns]
+        if sum(ks) != K:
+            raise ValueError("COALAQ1: kept-entry count mismatch")
+        idx, codes = unpack_entries(out[2], ustart, ns, ks, bits)
+        out[2], out[3] = idx, (out[3] if bits == RAW_BITS else codes)
     return (header, *out[:4], raw, ustart)

@@ -3121,6 +3121,106 @@ __global__ __launch_bounds__(BLOCK) void k_ef_commit_dense(Params P) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// compact payload (wire v3): entry j of the plan's idx / vals arrays as one (12 + B)-bit field
+//   field_j = (idx[j] & 0xFFF) | (code_j << 12)      B = bits (<= 8), or 0 at bits 32 (the fp32 values stay apart)
+// in a little-endian bit stream of uint32 words: field j occupies bits [j w, (j + 1) w), bit t of the stream is bit
+// t % 32 of word t / 32. The upper index bits are the entry's unit number, which the per-unit starts carry already.
+//   k_pack    a flat stream over the positions [0, total_k): a lane owns 32 consecutive entries = w whole words
+//   k_unpack  one wave per unit of the plan's table, its entry range from the starts (clamped as k_decode_lds clamps)
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t PACK_E = 32;  // entries per k_pack lane: 32 fields of w bits are exactly w words
+
+// B: code bits (0 = none: a raw plan's values are not read). idx and vals are 16-byte aligned (checked by the entry
+// point), so a full lane reads its 32 indices as eight b128 loads and its 32 codes as two.
+template <uint32_t B>
+__global__ __launch_bounds__(BLOCK) void k_pack(const int32_t* __restrict__ idx, const uint8_t* __restrict__ vals,
+                                                uint32_t* __restrict__ out, uint64_t K) {
+  constexpr uint32_t W = 12u + B;
+  const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const uint64_t j0 = t * PACK_E;
+  if (j0 >= K) return;
+  const uint32_t cnt = (uint32_t)min((uint64_t)PACK_E, K - j0);
+  uint32_t f[PACK_E];
+  if (cnt == PACK_E) {
+    const int4* pi = reinterpret_cast<const int4*>(idx + j0);
+#pragma unroll
+    for (uint32_t i = 0; i < PACK_E / 4; ++i) {
+      const int4 v = pi[i];
+      f[4 * i + 0] = (uint32_t)v.x & 0xFFFu;
+      f[4 * i + 1] = (uint32_t)v.y & 0xFFFu;
+      f[4 * i + 2] = (uint32_t)v.z & 0xFFFu;
+      f[4 * i + 3] = (uint32_t)v.w & 0xFFFu;
+    }
+    if (B != 0) {
+      const uint4* pv = reinterpret_cast<const uint4*>(vals + j0);
+#pragma unroll
+      for (uint32_t i = 0; i < PACK_E / 16; ++i) {
+        const uint4 v = pv[i];
+        const uint32_t q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t c = 0; c < 16; ++c) f[16 * i + c] |= ((q[c >> 2] >> ((c & 3u) * 8u)) & ((1u << B) - 1u)) << 12;
+      }
+    }
+  } else {  // the stream's last lane: entries past total_k are zero fields (the tail word's padding)
+#pragma unroll
+    for (uint32_t i = 0; i < PACK_E; ++i) {
+      f[i] = 0u;
+      if (i < cnt) {
+        f[i] = (uint32_t)idx[j0 + i] & 0xFFFu;
+        if (B != 0) f[i] |= ((uint32_t)vals[j0 + i] & ((1u << B) - 1u)) << 12;
+      }
+    }
+  }
+  uint32_t word[W];
+  uint64_t acc = 0;
+  uint32_t nb = 0, wi = 0;
+#pragma unroll
+  for (uint32_t i = 0; i < PACK_E; ++i) {  // (fully unrolled: nb and wi are compile-time values)
+    acc |= (uint64_t)f[i] << nb;
+    nb += W;
+    if (nb >= 32u) {
+      word[wi++] = (uint32_t)acc;
+      acc >>= 32;
+      nb -= 32u;
+    }
+  }
+  const uint32_t nw = (cnt * W + 31u) >> 5;  // words this lane owns (W for a full lane); every one written once
+  uint32_t* o = out + t * W;
+#pragma unroll
+  for (uint32_t i = 0; i < W; ++i)
+    if (i < nw) o[i] = word[i];
+}
+
+// one wave per unit, one lane per entry: the field's one or two words (the second only when the field straddles a
+// word and the word lies inside the stream's nwords), then idx = unit start | low 12 bits, vals = code. Whatever the
+// starts say, lo <= e < hi <= k: only positions out_off + [0, k) of the unit's own segment are written.
+template <bool RAW>
+__global__ __launch_bounds__(BLOCK) void k_unpack(Params P, const uint32_t* __restrict__ packed, uint64_t nwords,
+                                                  uint32_t w) {
+  const uint32_t u = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const uint32_t lane = lane_id();
+  const UnitDev U = P.units[u];
+  uint32_t lo = P.ustart[u];
+  uint32_t hi = P.ustart[min(u + 1, P.n_units - 1)];
+  lo = min(lo, U.k);
+  hi = max(lo, min(min(U.last ? U.k : hi, U.k), lo + U.len));
+  const uint32_t mask = (1u << w) - 1u;
+  uint8_t* vals = static_cast<uint8_t*>(P.vals);
+  for (uint32_t e = lo + lane; e < hi; e += 64) {
+    const uint64_t j = U.out_off + e;
+    const uint64_t bit = j * w;
+    const uint64_t wd = bit >> 5;
+    const uint32_t sh = (uint32_t)bit & 31u;
+    uint32_t v = packed[wd] >> sh;  // (wd < nwords: j < total_k and the stream holds total_k fields)
+    if (sh + w > 32u && wd + 1 < nwords) v |= packed[wd + 1] << (32u - sh);
+    v &= mask;
+    P.idx[j] = (int32_t)(U.start | (v & 0xFFFu));
+    if (!RAW) vals[j] = (uint8_t)(v >> 12);
+  }
+}
+
 // k_gather: n scalars of `bytes` each, from their own storage (one device pointer each), into one contiguous
 // buffer — an update's passthrough entries (BatchNorm's int64 num_batches_tracked, one per layer) snapshotted
 // in one launch instead of a stack of tensor copies
@@ -3500,6 +3600,32 @@ void launch_decode_lds(const Params& P, coalac_plan_t plan, hipStream_t st) {
   }
 }
 
+// the compact payload's geometry: field width and stream length of a plan
+uint32_t packed_field_bits(const coalac_plan* plan) { return 12u + (plan->bits == 32 ? 0u : (uint32_t)plan->bits); }
+uint64_t packed_words(const coalac_plan* plan) { return (plan->total_k * packed_field_bits(plan) + 31u) / 32u; }
+
+// the checks pack and unpack share; *done: nothing to launch (an empty plan)
+int packed_args(coalac_plan_t plan, const char* who, bool null_arg, uint64_t packed_bytes, bool* done) {
+  *done = false;
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if (null_arg) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  if (plan->dense)
+    return fail(COALAC_EINVAL, "%s: a dense plan's indices are implied, there is nothing to pack (wire v2 carries it)", who);
+  if (packed_bytes < 4 * packed_words(plan))
+    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
+                (unsigned long long)(4 * packed_words(plan)));
+  *done = plan->total_k == 0 || plan->proto.n_units == 0;
+  return *done ? COALAC_OK : check_device(plan);
+}
+
+template <uint32_t B = 0>
+void launch_pack(uint32_t b, dim3 g, hipStream_t st, const int32_t* idx, const uint8_t* vals, uint32_t* out, uint64_t K) {
+  if (b == B)
+    hipLaunchKernelGGL((k_pack<B>), g, dim3(BLOCK), 0, st, idx, vals, out, K);
+  else if constexpr (B < 8)
+    launch_pack<B + 1>(b, g, st, idx, vals, out, K);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3777,6 +3903,49 @@ int coalac_ef_commit(coalac_plan_t plan, const int32_t* d_idx, const void* d_val
           hipLaunchKernelGGL((k_ef_commit_dense<raw.value>), g, dim3(BLOCK), 0, st, P);
         else
           hipLaunchKernelGGL((k_ef_commit<raw.value>), g, dim3(BLOCK), 0, st, P);
+      },
+      plan->bits == 32);
+  return launched();
+}
+
+int coalac_plan_packed_bytes(coalac_plan_t plan, uint64_t* bytes) {
+  if (!plan || !bytes) return fail(COALAC_EINVAL, "coalac_plan_packed_bytes: plan or output pointer is NULL");
+  *bytes = 4 * packed_words(plan);
+  return COALAC_OK;
+}
+
+int coalac_pack(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, void* d_packed, uint64_t packed_bytes,
+                void* stream) {
+  bool done = false;
+  int rc = packed_args(plan, "coalac_pack", !d_idx || !d_vals || !d_packed, packed_bytes, &done);
+  if (rc || done) return rc;
+  if ((addr_bits(d_idx, d_vals) & 15) || (addr_bits(d_packed) & 3))
+    return fail(COALAC_EINVAL, "coalac_pack: idx / vals must be 16-byte aligned, packed 4-byte aligned");
+  const uint64_t lanes = (plan->total_k + PACK_E - 1) / PACK_E, blocks = (lanes + BLOCK - 1) / BLOCK;
+  if (blocks > 0x7FFFFFFFull) return fail(COALAC_EINVAL, "coalac_pack: plan too large");
+  launch_pack(packed_field_bits(plan) - 12u, dim3((uint32_t)blocks), static_cast<hipStream_t>(stream), d_idx,
+              static_cast<const uint8_t*>(d_vals), static_cast<uint32_t*>(d_packed), plan->total_k);
+  return launched();
+}
+
+int coalac_unpack(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const uint32_t* d_ustart,
+                  int32_t* d_idx, void* d_vals, void* stream) {
+  bool done = false;
+  int rc = packed_args(plan, "coalac_unpack", !d_packed || !d_ustart || !d_idx || !d_vals, packed_bytes, &done);
+  if (rc || done) return rc;
+  if (addr_bits(d_packed, d_ustart, d_idx) & 3)
+    return fail(COALAC_EINVAL, "coalac_unpack: packed / ustart / idx must be 4-byte aligned");
+  Params P = plan->proto;
+  P.ustart = d_ustart;
+  P.idx = d_idx;
+  P.vals = d_vals;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  const uint32_t* packed = static_cast<const uint32_t*>(d_packed);
+  with_flags(
+      [&](auto raw) {
+        hipLaunchKernelGGL((k_unpack<raw.value>), g, dim3(BLOCK), 0, st, P, packed, packed_bytes / 4,
+                           packed_field_bits(plan));
       },
       plan->bits == 32);
   return launched();

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define COALAC_ABI_VERSION 6
+#define COALAC_ABI_VERSION 7
 
 enum {
   COALAC_OK = 0,
@@ -59,7 +59,9 @@ enum {
  * the k_bounds / k_fill / k_scatter kernels and the staged (_sched) entry points; plans whose every segment keeps
  * all its elements run the dense codec, with the indices implied. ABI 6 adds the error-feedback pair
  * coalac_ef_accumulate / coalac_ef_commit — a client-side residual memory around an unchanged encode; no existing
- * entry point changes.) */
+ * entry point changes. ABI 7 adds the compact payload's coalac_plan_packed_bytes / coalac_pack / coalac_unpack — a
+ * lossless repacking of idx / vals after an unchanged encode and before an unchanged decode; again no existing entry
+ * point, plan query or workspace size changes.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -150,6 +152,29 @@ int coalac_ef_accumulate(coalac_plan_t plan, const float* d_in, const float* con
                          float* d_resid, void* stream);
 int coalac_ef_commit(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, const float* d_mn,
                      const float* d_scale, const uint32_t* d_ustart, float* d_resid, void* stream);
+
+/* Compact payload (wire v3): entry j of the plan's idx / vals arrays as one w-bit field, w = 12 + b, where b = bits
+ * (1..8) or 0 at bits 32 (the fp32 values then stay in d_vals and are neither packed nor unpacked):
+ *
+ *   field_j = (idx[j] & 0xFFF) | (code_j << 12)
+ *
+ * in a little-endian bit stream of uint32 words: field j occupies bits [j w, (j + 1) w), bit t of the stream is bit
+ * t % 32 of word t / 32; the stream is ceil(total_k w / 32) words long and its padding bits are zero. j is the position
+ * in idx / vals, so out_off, batched and explicit-row plans are honoured (an explicit-row plan packs every position
+ * below its total_k, its own or not). The upper bits of an index are its 4096-element unit's number, which the per-unit
+ * starts (d_ustart) already say: unit u of a segment, its u_s-th, owns the segment-relative entries
+ * [ustart[u], ustart[u + 1]) (the segment's last unit ends at k), clamped to [0, k] with begin <= end exactly as
+ * coalac_decode clamps; for each owned entry e, j = out_off + e, idx[j] = (u_s << 12) | (field_j & 0xFFF) and
+ * vals[j] = field_j >> 12. Whatever the starts say, unpack writes only idx[j] / vals[j] with
+ * out_off <= j < out_off + k of the unit's own segment.
+ * Each call is one asynchronous launch on `stream`: no allocation, no workspace, no host synchronisation. Any NULL
+ * pointer, a packed_bytes below coalac_plan_packed_bytes, or a dense plan (every k == n: its indices are implied and
+ * wire v2 carries it) is COALAC_EINVAL. coalac_pack needs d_idx and d_vals 16-byte aligned. */
+int coalac_plan_packed_bytes(coalac_plan_t plan, uint64_t* bytes);
+int coalac_pack(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, void* d_packed, uint64_t packed_bytes,
+                void* stream);
+int coalac_unpack(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const uint32_t* d_ustart,
+                  int32_t* d_idx, void* d_vals, void* stream);
 
 /* Profiling variants: identical work, plus hipEventRecord(events[i], stream) between kernels.
  * encode: [0] before k_sample, [1] after k_sample, [2] after k_scan, [3] after the select kernels
