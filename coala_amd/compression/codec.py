@@ -12,33 +12,38 @@ honours:
   * `calculate_model_size` calls `.parameters()` on whatever is in `self.model`
     (/root/reference/coala/client/base.py:155,474-487), so the carrier has a parameters() that reports
     its real payload size.
+
+State / layout description: state.py; blob validation: validate.py; decoded-module clone and recycling: clone.py
+(their public names are re-exported here).
 """
-import copy
+import ctypes
 import math
-import sys
 import threading
 from collections import OrderedDict
-from collections.abc import Mapping
-from itertools import chain, repeat
-from operator import attrgetter, is_, itemgetter
-
-import ctypes
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _lib, wire
+from ._cache import IdentityCache
+from .clone import _recipe, _reuse_after, _segment_views, module_with_state, release_decode_pool
 from .plan import CodecPlan, Encoded
-from .spec import ALIGN, RAW_BITS, UNIT, VALID_BITS, SegmentTable, align_up, k_for
-
-MODES = ("delta", "weights")
+from .spec import RAW_BITS, VALID_BITS
+from .state import (FlatState, RawState, as_numpy, describe_state, describe_tensors,  # noqa: F401 (re-exported)
+                    flatten_state, layout_of, module_tensors)
+from .state import (_check_same_layout, _data_ptr, _decode_layout, _dense_elements, _describe, _get_device,
+                    _is_contig, _layout, _layout_walk, _module_walk, _raw_snapshot, _to_host)
+from .validate import MODES, validate
 
 
 class HipBackend:
     """Default backend: hand-written HIP kernels behind the C ABI (coala_amd/csrc/coalac.hip)."""
 
     name = "hip"
+
+    def __init__(self):
+        self._gather_ptrs = IdentityCache(16)  # keyed by value: the scalars' pointers -> the same on the device
 
     def default_device(self):
         return torch.device("cuda", torch.cuda.current_device())
@@ -71,13 +76,7 @@ class HipBackend:
                 described.raw_ok = ok
             if not ok:
                 return None
-        cache = self.__dict__.setdefault("_gather_ptrs", OrderedDict())
-        d = cache.get(ptrs)
-        if d is None:
-            d = torch.tensor(ptrs, dtype=torch.int64).to(dev)
-            cache[ptrs] = d
-            while len(cache) > 16:
-                cache.popitem(last=False)
+        d = self._gather_ptrs.get((), ptrs, lambda: torch.tensor(ptrs, dtype=torch.int64).to(dev))
         st = torch.cuda.current_stream(dev)
         d.record_stream(st)  # (an eviction from the cache never hands its memory to a kernel still reading it)
         out = torch.empty(len(ts), dtype=t0.dtype, device=dev)
@@ -87,439 +86,12 @@ class HipBackend:
         return out
 
 
-class FlatState:
-    """A state_dict split into one aligned flat fp32 buffer (segments) plus raw passthrough entries."""
+_PACKED_HEADERS = IdentityCache(16)  # (layout entries; header fields, raw sizes) -> header JSON bytes
 
-    def __init__(self, entries, flat, raw):
-        self.entries = entries  # list of dicts: name, dtype, shape, kind, (seg, off, n) | ()
-        self.flat = flat        # fp32 [span] on device (None if no fp32 entry)
-        self.raw = raw          # OrderedDict name -> tensor
-        self._on = {}           # device -> flat copy (a snapshot taken on one device, used on another)
 
-    def flat_on(self, device):
-        """The flat buffer on `device` (copied once per device and cached: the w_global snapshot of a
-        round is immutable)."""
-        if self.flat is None or self.flat.device == torch.device(device):
-            return self.flat
-        key = str(device)
-        t = self._on.get(key)
-        if t is None:
-            t = self.flat.to(device)
-            self._on[key] = t
-        return t
-
-
-def layout_of(state):
-    """[(name, dtype str, shape)] of a state_dict — what must match between encoder and decoder."""
-    return [(k, str(v.dtype).replace("torch.", ""), tuple(v.shape)) for k, v in state.items()]
-
-
-_DTYPE_NAMES = {}
-
-
-def _dtype_name(dt):
-    n = _DTYPE_NAMES.get(dt)
-    if n is None:
-        n = _DTYPE_NAMES[dt] = str(dt).replace("torch.", "")
-    return n
-
-
-class _Layout:
-    """The header entries of one state_dict layout (the (name, dtype, shape) sequence) and the names of its
-    fp32 segments / raw passthrough entries. Built once per layout: a model's layout is fixed for a whole FL
-    task, and the per-entry Python of building them was most of a ResNet-50 encode call's host time. The
-    entries are shared by every header of that layout and never mutated."""
-
-    def __init__(self, items):
-        self.entries, self.seg_names, self.raw_names = [], [], []
-        self.seg_idx, self.raw_idx = [], []
-        off = seg = 0
-        for i, (name, dt, shape) in enumerate(items):
-            n = 1
-            for d in shape:
-                n *= d
-            e = {"name": name, "dtype": _dtype_name(dt), "shape": list(shape)}
-            if dt == torch.float32 and n > 0:
-                e.update(kind="seg", seg=seg, off=off, n=n)
-                self.seg_names.append(name)
-                self.seg_idx.append(i)
-                off = align_up(off + n)
-                seg += 1
-            else:
-                e["kind"] = "raw"
-                self.raw_names.append(name)
-                self.raw_idx.append(i)
-            self.entries.append(e)
-        self.sizes = [e["n"] for e in self.entries if e["kind"] == "seg"]
-        self.sizes_key = tuple(self.sizes)
-        # the passthrough entries as one group when they are all scalars of one dtype (BatchNorm counters)
-        raw_items = [items[i] for i in self.raw_idx]
-        self.raw_scalars = (None if not raw_items or any(len(sh) for _, _, sh in raw_items)
-                            or len({dt for _, dt, _ in raw_items}) != 1
-                            else [(n, (), 1) for n, _, _ in raw_items])
-
-
-_LAYOUTS = OrderedDict()
-_LAYOUTS_LOCK = threading.Lock()
-
-
-def _layout(state):
-    return _layout_sig(tuple((k, v.dtype, v.shape) for k, v in state.items()))
-
-
-def _layout_sig(sig):
-    with _LAYOUTS_LOCK:
-        L = _LAYOUTS.get(sig)
-        if L is None:
-            L = _LAYOUTS[sig] = _Layout(sig)
-            while len(_LAYOUTS) > 16:
-                _LAYOUTS.popitem(last=False)
-    return L
-
-
-_MOD_TABLES = itemgetter("_parameters", "_buffers", "_modules", "_non_persistent_buffers_set")
-
-
-class _StateWalk:
-    """The tensors of a module's state_dict, in state_dict order, without building the state_dict: the
-    module tree walked once (pre-order, as Module.state_dict recurses), then per call each module's
-    parameter and persistent-buffer tables read in place (no per-entry detach, no prefix strings, no
-    state-dict hooks: the reference's models register none). Re-walked when a table's size changes, when a
-    table object or a submodule is replaced (each module's children are compared by identity: a client that
-    keeps one root module across rounds may swap `model.head`), or when the non-persistent buffer set changes.
-    The per-call checks and the gather run as C-level maps over the modules' __dict__ tables (a Python loop
-    over ResNet-50's 161 modules cost more than the encode's own launches)."""
-
-    def __init__(self, module):
-        self.mods, names = [], []
-        srcs, keys = [], []  # per state entry: the table it lives in, its key
-        self.parents, self.npbs = [], []  # (module, children) of the modules with children; (module, set) likewise
-        self.hooked = False
-        for prefix, m in module.named_modules(remove_duplicate=False):
-            self.hooked = self.hooked or bool(m._state_dict_hooks or m._state_dict_pre_hooks)
-            pn = tuple(k for k, v in m._parameters.items() if v is not None)
-            bn = tuple(k for k, v in m._buffers.items() if v is not None and k not in m._non_persistent_buffers_set)
-            self.mods.append(m)
-            srcs.extend([m._parameters] * len(pn) + [m._buffers] * len(bn))
-            keys.extend(pn + bn)
-            if m._modules:
-                self.parents.append((m, tuple(m._modules.values())))
-            if m._non_persistent_buffers_set:
-                self.npbs.append((m, frozenset(m._non_persistent_buffers_set)))
-            p = prefix + "." if prefix else ""
-            names.extend(p + k for k in pn + bn)
-        self.dicts = [m.__dict__ for m in self.mods]
-        self.tables = self._tables()           # every module's 4 table objects, flattened
-        self.sizes = list(map(len, self.tables))
-        self.kid_dicts = [m._modules for m, _ in self.parents]
-        self.kids = [kids for _, kids in self.parents]
-        self.srcs, self.keys = srcs, keys
-        self.names = tuple(names)
-        self.last = None  # _Described: the last describe_tensors of these tensors
-
-    def _tables(self):
-        return list(chain.from_iterable(map(_MOD_TABLES, self.dicts)))
-
-    def tensors(self):
-        """The tensors, or None when the tree changed since the walk (a table's size or object, a replaced or
-        added submodule, the non-persistent buffer set): the caller walks again."""
-        tables = self._tables()
-        if list(map(len, tables)) != self.sizes or not all(map(is_, tables, self.tables)):
-            return None
-        if list(map(tuple, map(dict.values, self.kid_dicts))) != self.kids:  # (identity first: a swap is unequal)
-            return None
-        for m, npb in self.npbs:
-            if m._non_persistent_buffers_set != npb:
-                return None
-        return list(map(dict.__getitem__, self.srcs, self.keys))
-
-
-class _Described:
-    """describe_tensors' result for one list of tensors: reused while the same tensor objects sit at the same
-    storage (a dtype or shape change of a tensor in place moves its storage; a reshape of a parameter's .data
-    that keeps its storage start is not looked for)."""
-
-    __slots__ = ("tensors", "ptrs", "L", "seg_ptrs", "raw_ptrs", "raw_ok")
-
-    def __init__(self, tensors, ptrs, L):
-        self.tensors, self.ptrs, self.L = tensors, ptrs, L
-        self.seg_ptrs = tuple(ptrs[i] for i in L.seg_idx)
-        self.raw_ptrs = tuple(ptrs[i] for i in L.raw_idx)
-        self.raw_ok = None  # the gather's own checks of the raw scalars, once
-
-
-_WALKS = {}  # id(module) -> (weakref, _StateWalk)
-
-
-def module_tensors(module):
-    """(names, tensors) of module.state_dict() — the same names and tensor storage, in the same order — via a
-    cached _StateWalk. A module tree with state-dict hooks takes state_dict() itself."""
-    return _module_walk(module)[:2]
-
-
-def _module_walk(module):
-    """module_tensors' (names, tensors) and the walk (None when state_dict() was taken)."""
-    if module._state_dict_hooks or module._state_dict_pre_hooks:
-        st = module.state_dict()
-        return tuple(st), list(st.values()), None
-    hit = _WALKS.get(id(module))
-    w = hit[1] if hit is not None and hit[0]() is module else None
-    ts = w.tensors() if w is not None else None
-    if ts is None:  # first call, another module at this id, or a table changed size: walk again
-        import weakref
-        w = _StateWalk(module)
-        with _LAYOUTS_LOCK:
-            _WALKS[id(module)] = (weakref.ref(module), w)
-            if len(_WALKS) > 64:
-                for k in [k for k, (r, _) in _WALKS.items() if r() is None]:
-                    del _WALKS[k]
-        ts = w.tensors()
-    if w.hooked:
-        st = module.state_dict()
-        return tuple(st), list(st.values()), None
-    return w.names, ts, w
-
-
-_get_dtype, _get_shape = attrgetter("dtype"), attrgetter("shape")
-
-
-def describe_tensors(names, tensors, walk=None, gather=None):
-    """describe_state() over (names, tensors) in state_dict order (module_tensors). walk: the _StateWalk the
-    tensors came from — the layout is then reused while the same tensor objects sit at the same storage (see
-    _Described), instead of reading every tensor's dtype and shape. gather: a backend's one-launch copy of
-    one-element tensors (HipBackend.gather_scalars) for the passthrough scalars."""
-    d, segs = _layout_walk(names, tensors, walk)
-    return d.L, segs, _raw_snapshot(d, tensors, gather)
-
-
-def _layout_walk(names, tensors, walk):
-    """(_Described, fp32 segment tensors) of the tensors: the layout part of describe_tensors."""
-    ptrs = tuple(map(_data_ptr, tensors))
-    d = walk.last if walk is not None else None
-    if d is None or d.ptrs != ptrs or not all(map(is_, tensors, d.tensors)):
-        dts, shs = list(map(_get_dtype, tensors)), list(map(_get_shape, tensors))
-        d = _Described(tensors, ptrs, _layout_sig(tuple(zip(names, dts, shs))))
-        if walk is not None:
-            walk.last = d
-    return d, list(map(tensors.__getitem__, d.L.seg_idx))
-
-
-def _raw_snapshot(d, tensors, gather):
-    """The passthrough entries' RawState: one gather launch for a group of scalars of one dtype."""
-    L = d.L
-    raw_ts = list(map(tensors.__getitem__, L.raw_idx))
-    raw = None
-    if L.raw_scalars is not None:
-        flat = gather(raw_ts, d) if gather is not None else None
-        if flat is not None:
-            raw = RawState([(flat, L.raw_scalars)], L.raw_names)
-        else:
-            try:
-                with torch.no_grad():  # one stack of the scalar counters: no per-entry checks
-                    raw = RawState([(torch.stack(raw_ts), L.raw_scalars)], L.raw_names)
-            except RuntimeError:  # (counters on several devices)
-                raw = None
-    if raw is None:
-        raw = RawState.snapshot(list(zip(L.raw_names, raw_ts)))
-    return raw
-
-
-def describe_state(state):
-    """state_dict -> (entries as flatten_state would write them, fp32 segment tensors in order, raw
-    passthrough entries), WITHOUT copying the fp32 data: the zero-copy encode reads the tensors in place."""
-    L, segs, raw = _describe(state)
-    return L.entries, segs, raw
-
-
-def _describe(state):
-    L = _layout(state)
-    segs = [state[n] for n in L.seg_names]  # read in place by the kernels (pointer, numel, dtype, contiguity)
-    return L, segs, RawState.snapshot([(n, state[n]) for n in L.raw_names])
-
-
-_data_ptr, _is_contig, _get_device = torch.Tensor.data_ptr, torch.Tensor.is_contiguous, torch.Tensor.get_device
-
-
-_PACKED_HEADERS = OrderedDict()  # (layout entries id, fields, raw sizes) -> (entries, header JSON bytes)
-
-
-def _to_host(*ts):
-    """numpy copies of tensors, with ONE device-to-host transfer when they live on a GPU."""
-    if not ts or ts[0].device.type == "cpu":
-        return [t.numpy() for t in ts]
-    parts = [t.contiguous().view(torch.uint8).reshape(-1) for t in ts]
-    host = torch.cat(parts).cpu().numpy()
-    out, o = [], 0
-    for t, p in zip(ts, parts):
-        n = p.numel()
-        out.append(host[o:o + n].view(_NP_DTYPES[t.dtype]))
-        o += n
-    return out
-
-
-_NP_DTYPES = {torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8, torch.int64: np.int64,
-              torch.uint32: np.uint32}
-# the dtypes a passthrough entry of a blob may name (a state_dict's non-fp32 or empty entries); a blob naming
-# anything else is rejected rather than handed to getattr(torch, ...)
-_RAW_DTYPES = {_dtype_name(d): d for d in (torch.float32, torch.float64, torch.float16, torch.bfloat16, torch.int64,
-                                          torch.int32, torch.int16, torch.int8, torch.uint8, torch.bool,
-                                          torch.complex64, torch.complex128)}
-
-
-class RawState(Mapping):
-    """The passthrough (non-fp32) entries of an update — BatchNorm's int64 num_batches_tracked and the like —
-    held as ONE flat tensor per (dtype, device) with the entries' names and shapes, in state order. Taking
-    the snapshot is one copy kernel per group (not one per entry); the per-entry tensors are views made on
-    first access (one unbind / split call per group). A read-only mapping name -> tensor."""
-
-    def __init__(self, groups, order):
-        self._groups = groups    # [(flat, [(name, shape, numel)])]
-        self._order = order      # names in state order
-        self._views = None
-
-    @classmethod
-    def snapshot(cls, items):
-        """Copies of (name, tensor) items taken now, grouped per (dtype, device)."""
-        groups, index = [], {}
-        for name, t in items:
-            key = (t.dtype, t.device)
-            g = index.get(key)
-            if g is None:
-                g = index[key] = []
-                groups.append((key, g))
-            g.append((name, t))
-        out = []
-        with torch.no_grad():
-            for _, members in groups:
-                ts = [t for _, t in members]
-                if all(t.dim() == 0 for t in ts):
-                    flat = torch.stack(ts)  # (one kernel: the usual case, scalar counters)
-                else:
-                    flat = torch.cat([t.reshape(-1) for t in ts])
-                out.append((flat, [(n, tuple(t.shape), t.numel()) for n, t in members]))
-        return cls(out, [n for n, _ in items])
-
-    def _make_views(self, groups):
-        views = {}
-        for flat, members in groups:
-            if all(len(shape) == 0 for _, shape, _ in members):
-                views.update(zip((n for n, _, _ in members), flat.unbind()))
-            else:
-                for (n, shape, _), piece in zip(members, flat.split_with_sizes([m for _, _, m in members])):
-                    views[n] = piece.view(shape)
-        return views
-
-    def __getitem__(self, name):
-        if self._views is None:
-            self._views = self._make_views(self._groups)
-        return self._views[name]
-
-    def __iter__(self):
-        return iter(self._order)
-
-    def __len__(self):
-        return len(self._order)
-
-    @property
-    def nbytes(self):
-        return sum(f.numel() * f.element_size() for f, _ in self._groups)
-
-    @classmethod
-    def from_entries(cls, entries, rawb):
-        """From a blob's raw section: entries with "dtype", "shape", "off", "nbytes" (in state order). Runs of
-        same-dtype entries stored back to back become one tensor (one copy of the bytes)."""
-        groups, order, run = [], [], []
-
-        def flush():
-            if run:
-                dt = _RAW_DTYPES.get(run[0]["dtype"])
-                if dt is None:
-                    raise ValueError(f"COALAQ1: unsupported raw entry dtype {run[0]['dtype']!r}")
-                size = torch.empty(0, dtype=dt).element_size()
-                members = []
-                for e in run:  # every entry's byte count must match its own shape (not only the run's total)
-                    m = int(np.prod(e["shape"], dtype=np.int64))
-                    if m < 0 or int(e["nbytes"]) != m * size:
-                        raise ValueError(f"COALAQ1: raw entry {e['name']!r}: {e['nbytes']} bytes for shape "
-                                         f"{e['shape']} of {e['dtype']}")
-                    members.append((e["name"], tuple(e["shape"]), m))
-                lo, hi = run[0]["off"], run[-1]["off"] + run[-1]["nbytes"]
-                if lo < 0 or hi > len(rawb):
-                    raise ValueError("COALAQ1: raw entries past the end of the blob")
-                buf = bytearray(rawb[lo:hi])
-                flat = torch.frombuffer(buf, dtype=dt) if buf else torch.empty(0, dtype=dt)
-                groups.append((flat, members))
-                run.clear()
-        for e in entries:
-            if run and (e["dtype"] != run[-1]["dtype"] or e["off"] != run[-1]["off"] + run[-1]["nbytes"]):
-                flush()
-            run.append(e)
-            order.append(e["name"])
-        flush()
-        return cls(groups, order)
-
-    def entry_bytes(self):
-        """{name: little-endian bytes} with one device-to-host copy per group."""
-        out = {}
-        for flat, members in self._groups:
-            b = flat.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()
-            per = flat.element_size()
-            o = 0
-            for n, _, m in members:
-                out[n] = b[o:o + m * per]
-                o += m * per
-        return {n: out[n] for n in self._order}
-
-    def fresh(self, device=None):
-        """{name: tensor} with storage of its own (one copy per group, onto `device` if given): what a
-        decode hands out, so decoded modules never alias the update or each other."""
-        return self.fresh_groups(device)[1]
-
-    def fresh_groups(self, device=None):
-        """(the per-group flat copies, fresh()'s {name: view of them})."""
-        groups = [(f.to(device, copy=True) if device is not None else f.clone(), m) for f, m in self._groups]
-        views = self._make_views(groups)
-        return [f for f, _ in groups], {n: views[n] for n in self._order}
-
-    def signature(self):
-        """What a copy into another RawState's group buffers needs to match: dtype, size and members per group."""
-        return tuple((f.dtype, f.numel(), tuple(m)) for f, m in self._groups)
-
-
-def _snapshot_raw(raw):
-    """Copies of the passthrough entries taken now (RawState: one copy kernel per dtype / device)."""
-    return RawState.snapshot(list(raw.items()))
-
-
-def flatten_state(state, device=None):
-    """state_dict -> FlatState with every fp32 entry at an ALIGN-aligned offset of one flat buffer.
-
-    One torch.cat over the tensors and zero pads (a single device copy kernel), not one copy per entry.
-    """
-    entries, parts, raw = [], [], OrderedDict()
-    off = seg = 0
-    pad_src = None
-    for name, t in state.items():
-        e = {"name": name, "dtype": str(t.dtype).replace("torch.", ""), "shape": list(t.shape)}
-        if t.dtype == torch.float32 and t.numel() > 0:
-            if device is None:
-                device = t.device
-            n = t.numel()
-            e.update(kind="seg", seg=seg, off=off, n=n)
-            parts.append(t.detach().reshape(-1).to(device))
-            pad = align_up(off + n) - (off + n)
-            if pad:
-                if pad_src is None:
-                    pad_src = torch.zeros(ALIGN, dtype=torch.float32, device=device)
-                parts.append(pad_src[:pad])
-            off += n + pad
-            seg += 1
-        else:
-            e.update(kind="raw")
-            raw[name] = t.detach().clone()
-        entries.append(e)
-    flat = torch.cat(parts) if parts else None
-    return FlatState(entries, flat, raw)
+def _raw_nbytes(raw):
+    """Bytes of an update's passthrough entries (a RawState, or a plain {name: tensor})."""
+    return raw.nbytes if isinstance(raw, RawState) else sum(t.numel() * t.element_size() for t in raw.values())
 
 
 class CompressedUpdate:
@@ -531,9 +103,7 @@ class CompressedUpdate:
     """
 
     def __init__(self, header, encoded, raw, blob=None, packed=None):
-        self.header = header
-        self.encoded = encoded
-        self.raw = raw
+        self.header, self.encoded, self.raw = header, encoded, raw
         # a compact carrier's packed entry stream (uint32[P]): the device buffer the encode packed, or None until
         # first asked for (encoded buffers on the CPU, or a backend without pack); shared by every deep copy
         self._packed = [packed]
@@ -542,15 +112,10 @@ class CompressedUpdate:
         self._blob = [blob]
 
     def __deepcopy__(self, memo):
-        # The encoded payload is immutable after encode: a deep copy shares it (and the packed blob)
-        # instead of a D2H + pack + unpack round trip through __getstate__/__setstate__.
-        other = CompressedUpdate.__new__(CompressedUpdate)
-        other.header = dict(self.header)  # (its "entries" list is shared and never mutated)
-        other.encoded = self.encoded
-        other.raw = self.raw
-        other._blob = self._blob
-        other._packed = self._packed
-        memo[id(self)] = other
+        # The encoded payload is immutable after encode: a deep copy shares it (and the packed blob, and the header's
+        # "entries" list, never mutated) instead of a D2H + pack + unpack round trip through __getstate__/__setstate__.
+        other = memo[id(self)] = CompressedUpdate.__new__(CompressedUpdate)
+        other.__dict__.update(self.__dict__, header=dict(self.header))
         return other
 
     @property
@@ -570,8 +135,7 @@ class CompressedUpdate:
         h = self.header
         vb = 4 if h["bits"] == RAW_BITS else 1
         ib = 0 if h["ratio"] >= 1.0 else 4  # ratio 1: indices implied, not shipped (wire.py "dense")
-        raw_b = self.raw.nbytes if isinstance(self.raw, RawState) else \
-            sum(t.numel() * t.element_size() for t in self.raw.values())
+        raw_b = _raw_nbytes(self.raw)
         if h.get("compact"):  # the packed stream, and the values only as fp32
             return (8 * h["n_segments"] + 4 * wire.packed_words(h["total_k"], h["bits"])
                     + (4 * h["total_k"] if h["bits"] == RAW_BITS else 0) + 4 * h["n_units"] + raw_b)
@@ -589,34 +153,25 @@ class CompressedUpdate:
         return self._blob[0]
 
     def _pack(self):
-        h = dict(self.header)
+        h = self.header
         raw = self.raw
         rawb = raw.entry_bytes() if isinstance(raw, RawState) else {
             n: (t.cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes() if t.numel() else b"")
             for n, t in raw.items()}
-        # the header (with each raw entry's blob offset) depends on the layout and the raw byte counts only
-        sizes = tuple(len(rawb[n]) for n in rawb)
-        key = (id(h["entries"]), h["ratio"], h["bits"], h["mode"], h["n_segments"], h.get("total_k"),
-               h.get("n_units"), sizes, bool(h.get("compact")))
-        hit = _PACKED_HEADERS.get(key)
-        if hit is not None and hit[0] is h["entries"]:
-            hjson = hit[1]
-        else:
-            raw_entries, pos = [], 0
+
+        def header_json():
+            entries, pos = [], 0
             for e in h["entries"]:
                 if e["kind"] == "raw":
                     nb = len(rawb[e["name"]])
                     e = dict(e, off=pos, nbytes=nb)
                     pos += nb
-                raw_entries.append(e)
-            h["entries"] = raw_entries
-            if h["ratio"] >= 1.0:
-                h["dense"] = True
-            hjson = wire.encode_header(h)
-            with _LAYOUTS_LOCK:
-                _PACKED_HEADERS[key] = (self.header["entries"], hjson)
-                while len(_PACKED_HEADERS) > 16:
-                    _PACKED_HEADERS.popitem(last=False)
+                entries.append(e)
+            return wire.encode_header(dict(h, entries=entries, **({"dense": True} if h["ratio"] >= 1.0 else {})))
+        # the header (with each raw entry's blob offset) depends on the layout and the raw byte counts only
+        hjson = _PACKED_HEADERS.get(h["entries"], (h["ratio"], h["bits"], h["mode"], h["n_segments"], h.get("total_k"),
+                                                   h.get("n_units"), tuple(map(len, rawb.values())),
+                                                   bool(h.get("compact"))), header_json)
         enc = self.encoded
         rawbytes = b"".join(rawb[e["name"]] for e in h["entries"] if e["kind"] == "raw")
         if h.get("compact"):  # wire v3: the packed stream instead of idx and the uint8 codes, neither copied
@@ -689,30 +244,12 @@ class CompressedUpdate:
     @property
     def compression_ratio(self):
         """Dense fp32 (+ raw) bytes of the update / its payload bytes."""
-        h = self.header
-        dense = 4 * _dense_elements(h["entries"])
-        dense += self.raw.nbytes if isinstance(self.raw, RawState) else \
-            sum(t.numel() * t.element_size() for t in self.raw.values())
-        return dense / max(1, self.nbytes)
+        return (4 * _dense_elements(self.header["entries"]) + _raw_nbytes(self.raw)) / max(1, self.nbytes)
 
     def __repr__(self):
         h = self.header
         return (f"CompressedUpdate(mode={h['mode']}, ratio={h['ratio']}, bits={h['bits']}, "
                 f"segments={h['n_segments']}, kept={h['total_k']}, bytes={self.nbytes})")
-
-
-_DENSE = OrderedDict()  # id(entries) -> (entries, fp32 elements)
-
-
-def _dense_elements(entries):
-    hit = _DENSE.get(id(entries))
-    if hit is None or hit[0] is not entries:
-        hit = (entries, sum(e["n"] for e in entries if e["kind"] == "seg"))
-        with _LAYOUTS_LOCK:
-            _DENSE[id(entries)] = hit
-            while len(_DENSE) > 32:
-                _DENSE.popitem(last=False)
-    return hit[1]
 
 
 def _all_kept(plan):
@@ -724,79 +261,23 @@ def _all_kept(plan):
     return dense
 
 
-_VALIDATED = OrderedDict()  # (id(entries), ratio, n_segments, total_k) -> (entries, ns_rep, first, units) of a layout
+def _delta_base(mode, entries, base, device, missing):
+    """A delta-mode update's base on `device` — the flat fp32 buffer of the global-model snapshot `base`, which
+    must be there (else ValueError(missing)) and of the update's layout — or None in "weights" mode."""
+    if mode != "delta":
+        return None
+    if base is None:
+        raise ValueError(missing)
+    _check_same_layout(entries, base.entries)
+    # the snapshot may have been taken where the global model arrived (the reference client's
+    # set_model runs before pretrain moves the model to its device, client/base.py:138 vs :245)
+    return base.flat_on(device)
 
 
-def validate(header, idx, ustart=None):
-    """Check an (untrusted) blob's index lists: per fp32 segment, k = k_for(n, ratio) entries, strictly
-    increasing, inside [0, n); and (wire v2) the per-unit starts: exactly the lower bounds of every unit's
-    first element in its segment's list. The decode kernels are bounds-safe anyway; this turns a corrupt
-    upload into an error instead of a silently wrong model. The header's structure is checked once per layout
-    (headers of one layout share their entries list: wire._parse_header); the indices every call."""
-    if header.get("bits") not in VALID_BITS or header.get("mode") not in MODES:
-        raise ValueError("COALAQ1: bad bits/mode")
-    entries = header["entries"]
-    key = (id(entries), float(header["ratio"]), int(header["n_segments"]), int(header["total_k"]))
-    hit = _VALIDATED.get(key)
-    if hit is None or hit[0] is not entries:
-        hit = (entries,) + _validate_layout(header)
-        with _LAYOUTS_LOCK:
-            _VALIDATED[key] = hit
-            while len(_VALIDATED) > 32:
-                _VALIDATED.popitem(last=False)
-    _, ns_rep, first, units = hit
-    if header.get("dense"):  # implied indices (0..n-1 per segment): nothing to check beyond the layout
-        if idx.size != 0 or ustart is not None:
-            raise ValueError("COALAQ1: a dense update carries no indices or starts")
-        return
-    if idx.size != int(header["total_k"]):
-        raise ValueError("COALAQ1: kept-entry count mismatch")
-    if ustart is not None and (units is None or int(header.get("n_units", -1)) != units[0].size
-                               or ustart.size != units[0].size):
-        raise ValueError("COALAQ1: per-unit start count mismatch")
-    if ns_rep is None:
-        return
-    if idx.size and (int(idx.min()) < 0 or np.any(idx >= ns_rep)):
-        raise ValueError("COALAQ1: index out of range")
-    d = np.diff(idx, prepend=np.int32(-1))
-    if np.any((d <= 0) & ~first):
-        raise ValueError("COALAQ1: indices not strictly increasing")
-    if ustart is not None:
-        # every entry's global unit (non-decreasing, the indices being sorted per segment): a unit starts where
-        # the first entry of that unit or a later one sits, relative to its segment's first entry
-        unit_seg_out, unit_base_rep, arange_u = units
-        gu = unit_base_rep + (idx >> 12)
-        if not np.array_equal(np.searchsorted(gu, arange_u) - unit_seg_out, ustart):
-            raise ValueError("COALAQ1: per-unit starts inconsistent with the indices")
-
-
-def _validate_layout(header):
-    segs = [e for e in header["entries"] if e["kind"] == "seg"]
-    if len(segs) != int(header["n_segments"]):
-        raise ValueError("COALAQ1: segment count mismatch")
-    # the decoder slices its output with the offsets it derives itself (SegmentTable of the sizes); a
-    # header whose own offsets / sizes disagree with that, or with the tensor shapes, is corrupt
-    table = SegmentTable([e["n"] for e in segs], header["ratio"], 1) if segs else None
-    for i, e in enumerate(segs):
-        if int(e["seg"]) != i or int(e["n"]) != int(np.prod(e["shape"], dtype=np.int64)) or \
-                int(e["off"]) != table.offsets[i]:
-            raise ValueError(f"COALAQ1: segment entry {e.get('name')!r} has inconsistent seg/n/off/shape")
-    ks = np.array([k_for(e["n"], header["ratio"]) for e in segs], dtype=np.int64)
-    if int(ks.sum()) != int(header["total_k"]):
-        raise ValueError("COALAQ1: kept-entry count mismatch")
-    if not ks.size:
-        return None, None, None
-    ns = np.array([e["n"] for e in segs], dtype=np.int32)
-    ns_rep = np.repeat(ns, ks)  # each entry's segment size
-    first = np.zeros(int(ks.sum()), dtype=bool)  # each segment's first entry (no predecessor to compare)
-    first[np.cumsum(ks)[:-1][ks[1:] > 0] if ks.size > 1 else []] = True
-    first[0] = True
-    # wire v2: per unit its segment's first entry; per entry its segment's first global unit
-    nu = (ns.astype(np.int64) + UNIT - 1) // UNIT
-    seg_out = np.concatenate([[0], np.cumsum(ks)[:-1]]).astype(np.int64)
-    unit_base = np.concatenate([[0], np.cumsum(nu)[:-1]]).astype(np.int32)
-    units = (np.repeat(seg_out, nu), np.repeat(unit_base, ks), np.arange(int(nu.sum()), dtype=np.int32))
-    return ns_rep, first, units
+def _copy_raw_groups(raw, into, non_blocking=False):
+    """An update's passthrough groups copied into a recycled skeleton's raw buffers."""
+    for dst, (src, _) in zip(into.raws, raw._groups):
+        dst.copy_(src, non_blocking=non_blocking)
 
 
 class UpdateCodec:
@@ -829,7 +310,7 @@ class UpdateCodec:
         self.compact = bool(compact)
         self.backend = backend if backend is not None else HipBackend()
         self._plans = {}
-        self._plan_fast = OrderedDict()  # (id(sizes), ratio, bits, clients) -> (sizes, device, plan)
+        self._plan_fast = IdentityCache(32)  # (sizes object; ratio, bits, clients, device) -> plan
         self._checked_ptrs = {}  # id(plan) -> the segment pointers of the last in-place encode that passed the checks
         self._ws = OrderedDict()
         self._lock = threading.Lock()
@@ -837,16 +318,8 @@ class UpdateCodec:
 
     def plan_for(self, sizes, device, ratio=None, bits=None, clients=1):
         # (per sizes OBJECT — a layout's cached tuple — no hash of a 161-entry tuple per hook call)
-        fk = (id(sizes), ratio, bits, clients)
-        hit = self._plan_fast.get(fk)
-        if hit is not None and hit[0] is sizes and hit[1] == device:
-            return hit[2]
-        p = self._plan_for(sizes, device, ratio, bits, clients)
-        with self._lock:
-            self._plan_fast[fk] = (sizes, device, p)
-            while len(self._plan_fast) > 32:
-                self._plan_fast.popitem(last=False)
-        return p
+        return self._plan_fast.get((sizes,), (ratio, bits, clients, device),
+                                   self._plan_for, sizes, device, ratio, bits, clients)
 
     def _plan_for(self, sizes, device, ratio, bits, clients):
         ratio = self.ratio if ratio is None else float(ratio)
@@ -914,10 +387,10 @@ class UpdateCodec:
         if residual is not None and self.mode != "delta":
             raise ValueError(f"error feedback (residual=) needs mode 'delta', not {self.mode!r}: the memory holds "
                              "what earlier updates dropped, which only adds to an update, never to the weights")
-        if self.mode == "delta" and base is None:
-            raise ValueError("delta mode needs the global-model snapshot (base)")
-        entries = L.entries
-        sizes = L.sizes
+        need_base = "delta mode needs the global-model snapshot (base)"
+        if self.mode == "delta" and base is None:  # (also of a state without fp32 entries, which returns below)
+            raise ValueError(need_base)
+        entries, sizes = L.entries, L.sizes
         header = {"ratio": self.ratio, "bits": self.bits, "mode": self.mode, "n_segments": len(sizes),
                   "entries": entries}
         if not sizes:
@@ -926,12 +399,7 @@ class UpdateCodec:
             z = torch.zeros(0)
             return CompressedUpdate(header, Encoded(z.int(), z.to(torch.uint8), z, z), raw)
         device = torch.device(device)
-        base_flat = None
-        if self.mode == "delta":
-            _check_same_layout(entries, base.entries)
-            # the snapshot may have been taken where the global model arrived (the reference client's
-            # set_model runs before pretrain moves the model to its device, client/base.py:138 vs :245)
-            base_flat = base.flat_on(device)
+        base_flat = _delta_base(self.mode, entries, base, device, need_base)
         plan = self.plan_for(L.sizes_key, device)
         if residual is not None:
             if getattr(plan, "ef_accumulate", None) is None or getattr(plan, "ef_commit", None) is None:
@@ -1027,12 +495,11 @@ class UpdateCodec:
 
     def _workspace(self, plan, stream=None):
         """The encode workspace of `plan` for this thread and `stream` (default: the current one), reused across
-        calls (kernels on
-        one stream run in order, so consecutive encodes of one thread can share it). Keyed by thread too: two
-        threads encoding on one stream (e.g. both on the default stream) interleave their launches, since the
-        ctypes call releases the GIL, and one encode's select would read the other's scan results. A bounded
-        LRU: an evicted workspace was allocated on its stream, whose later allocations are the only ones that
-        can reuse it (stream-ordered)."""
+        calls (kernels on one stream run in order, so consecutive encodes of one thread can share it). Keyed by thread
+        too: two threads encoding on one stream (e.g. both on the default stream) interleave their launches, since
+        the ctypes call releases the GIL, and one encode's select would read the other's scan results. A bounded
+        LRU: an evicted workspace was allocated on its stream, whose later allocations are the only ones that can
+        reuse it (stream-ordered)."""
         if not hasattr(plan, "empty_workspace"):
             return None
         if stream is None:
@@ -1085,12 +552,8 @@ class UpdateCodec:
         if D.sizes:
             if device is None:
                 device = self.backend.default_device()
-            base_flat = None
-            if h["mode"] == "delta":
-                if base is None:
-                    raise ValueError("delta-mode update needs the global model (base) to decode")
-                _check_same_layout(h["entries"], base.entries)
-                base_flat = base.flat_on(device)
+            base_flat = _delta_base(h["mode"], h["entries"], base, device,
+                                    "delta-mode update needs the global model (base) to decode")
             plan = self.plan_for(D.sizes, device, ratio=h["ratio"], bits=h["bits"])
             if device.type == "cuda":
                 cur = torch.cuda.current_stream(device)
@@ -1105,8 +568,7 @@ class UpdateCodec:
                     self._staged(side)
                     flat = plan.decode(enc, base=base_flat, out=out, stream=side)
                     if into is not None:
-                        for dst, (src, _) in zip(into.raws, raw._groups):
-                            dst.copy_(src, non_blocking=True)
+                        _copy_raw_groups(raw, into, non_blocking=True)
                 cur.wait_stream(side)
             else:
                 if into is not None:
@@ -1114,11 +576,9 @@ class UpdateCodec:
                 enc = update.encoded.to(device, non_blocking=True)
                 flat = plan.decode(enc, base=base_flat, out=None if into is None else into.flat)
                 if into is not None:
-                    for dst, (src, _) in zip(into.raws, raw._groups):
-                        dst.copy_(src)
+                    _copy_raw_groups(raw, into)
         elif into is not None:
-            for dst, (src, _) in zip(into.raws, raw._groups):
-                dst.copy_(src)
+            _copy_raw_groups(raw, into)
         if into is not None:
             return None, flat, into.raws
         vals = [None] * len(D.names)
@@ -1192,12 +652,8 @@ class UpdateCodec:
                 raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode / payload format")
         sizes = [e["n"] for e in h0["entries"] if e["kind"] == "seg"]
         device = self.backend.default_device() if device is None else torch.device(device)
-        base_flat = None
-        if h0["mode"] == "delta":
-            if base is None:
-                raise ValueError("delta-mode updates need the global model (base) to aggregate")
-            _check_same_layout(h0["entries"], base.entries)
-            base_flat = base.flat_on(device)
+        base_flat = _delta_base(h0["mode"], h0["entries"], base, device,
+                                "delta-mode updates need the global model (base) to aggregate")
         state = OrderedDict()
         flat = None
         # the output module is recycled like decode_module's (the same pool: modules this codec returned that
@@ -1225,7 +681,6 @@ class UpdateCodec:
                               torch.cat([e.ustart for e in encs]) if all(e.ustart is not None for e in encs) else None)
             avg_mask = None
             if params_only:
-                pnames = {n for n, _ in template.named_parameters(remove_duplicate=False)}
                 avg_mask = [e["name"] in pnames for e in h0["entries"] if e["kind"] == "seg"]
             flat = plan.aggregate(batched, weights, total=total, base=base_flat, mode=mode, avg_mask=avg_mask,
                                   out=None if sk is None else sk.flat)
@@ -1271,8 +726,8 @@ def _aggregate_raw(updates, weights, total, mode, device, keep=None, accs=None):
     if not all(isinstance(r, RawState) for r in raws):
         return None
     g0 = raws[0]._groups
-    sig = [(f.dtype, f.numel(), tuple(m)) for f, m in g0]
-    if any([(f.dtype, f.numel(), tuple(m)) for f, m in r._groups] != sig for r in raws[1:]):
+    sig = raws[0].signature()
+    if any(r.signature() != sig for r in raws[1:]):
         return None
     out = {}
     int_weights = all(type(w) is int and -(1 << 62) < w < (1 << 62) for w in weights)
@@ -1299,478 +754,3 @@ def _aggregate_raw(updates, weights, total, mode, device, keep=None, accs=None):
         for n, _, _ in members:
             out[n] = firsts[n] if keep is not None and keep(n) else views[n]
     return out
-
-
-def _segment_views(flat, table, entries):
-    """Views of the decoded flat buffer, one per fp32 segment (in segment order), shaped like the header's
-    entries, at the decoder's own offsets (never the untrusted header's): ONE split of the buffer into
-    segments and alignment pads, and a view only where a shape is not already the 1-D piece (a slice +
-    view per entry cost ~3 us each, ~1 ms per ResNet-50 decode)."""
-    split = table.__dict__.get("_split")
-    if split is None:
-        sizes, keep, prev = [], [], 0
-        for off, n in zip(table.offsets, table.sizes):
-            if off > prev:
-                sizes.append(off - prev)
-            keep.append(len(sizes))
-            sizes.append(n)
-            prev = off + n
-        split = table.__dict__["_split"] = (sizes, keep, prev)
-    sizes, keep, end = split
-    pieces = flat[:end].split_with_sizes(sizes)
-    seg_entries = [e for e in entries if e["kind"] == "seg"]
-    out = []
-    for j, e in zip(keep, seg_entries):
-        t, shape = pieces[j], e["shape"]
-        out.append(t if len(shape) == 1 else t.view(shape))
-    return out
-
-
-_PLAIN_TYPES = frozenset((bool, int, float, complex, str, bytes, type(None), torch.dtype, torch.device))
-_CONTAINER_TYPES = frozenset((dict, OrderedDict, list, set))
-_MODULE_TABLES = frozenset(("_parameters", "_buffers", "_modules"))
-_TABLES3 = itemgetter("_parameters", "_buffers", "_modules")
-_make_param = torch.Tensor._make_subclass
-
-
-def _plain(v):
-    """An attribute value a clone may share with the template: immutable and holding no tensor / module."""
-    tv = type(v)
-    if tv in _PLAIN_TYPES:
-        return True
-    if tv is tuple or tv is frozenset:
-        return all(_plain(x) for x in v)
-    return False
-
-
-class _TreeRecipe:
-    """How to rebuild a template's module tree around new tensors, classified once per template (the
-    server's global model is one object for the whole task): the modules in pre-order (a submodule shared
-    by several parents is cloned once, as copy.deepcopy would), and per module the attributes a clone
-    shares (immutable plain values), gets as fresh empty containers (hook dicts, ...), deep-copies (any
-    other object: non-empty containers, hook objects, unregistered modules — with a memo that maps the
-    template's modules / parameters / buffers to the clone's, so bound hooks are rebound as deepcopy would)
-    or clones (unregistered tensors), plus its parameter / buffer / child slots. A module whose attribute
-    set, table sizes or special attribute types changed since is re-classified."""
-
-    def __init__(self, template):
-        self.pool, self.pool_lock = [], threading.Lock()
-        self.tick = 0  # idle_skeleton calls so far (a pooled tree's last use is one of these)
-        self.mods, self.prefixes, self.index = [], [], {}
-        stack = [(template, "")]
-        while stack:
-            m, prefix = stack.pop()
-            if id(m) in self.index:
-                continue
-            self.index[id(m)] = len(self.mods)
-            self.mods.append(m)
-            self.prefixes.append(prefix)
-            stack.extend((c, prefix + n + ".") for n, c in reversed(list(m._modules.items())) if c is not None)
-        self.info = [self.classify(m, p) for m, p in zip(self.mods, self.prefixes)]
-
-    def classify(self, m, prefix):
-        d = m.__dict__
-        fresh, deep, tens = [], [], []
-        for k, v in d.items():
-            if k in _MODULE_TABLES or _plain(v):
-                continue
-            tv = type(v)
-            if tv in _CONTAINER_TYPES and not v:
-                fresh.append((k, tv))
-            elif isinstance(v, torch.Tensor):
-                tens.append((k, tv))
-            else:
-                deep.append((k, tv))
-        params = tuple((n, prefix + n, p is None or p.requires_grad) for n, p in m._parameters.items())
-        buffers = tuple((n, prefix + n) for n in m._buffers)
-        children = tuple((n, None if c is None else self.index[id(c)]) for n, c in m._modules.items())
-        sizes = (len(d), len(m._parameters), len(m._buffers), len(m._modules))
-        return sizes, tuple(fresh), tuple(deep), tuple(tens), params, buffers, children
-
-    def valid(self, i):
-        """Cheap per-call check that module i still matches its classification: attribute / table sizes, its
-        fresh containers still empty (a hook registered later must be deep-copied, not dropped) and the
-        types of its deep-copied / cloned attributes."""
-        m = self.mods[i]
-        sizes, fresh, deep, tens = self.info[i][:4]
-        d = m.__dict__
-        if sizes != (len(d), len(m._parameters), len(m._buffers), len(m._modules)):
-            return False
-        g = self.getters[i]
-        if g is not None and any(g(d)):
-            return False
-        return not (tens or deep) or all(type(d.get(k)) is tv for k, tv in tens + deep)
-
-    def _getters(self):
-        from operator import itemgetter
-        self.getters = []
-        for info in self.info:
-            keys = [k for k, _ in info[1]]
-            self.getters.append(None if not keys else itemgetter(*keys) if len(keys) > 1 else
-                                (lambda d, k=keys[0]: (d[k],)))
-
-    def _current(self):
-        """Re-classify the template modules that changed since (attribute / table sizes, hooks registered, the
-        types of special attributes); returns the per-module fast tables. A change also retires every pooled
-        skeleton (they were built from the old classification)."""
-        mods, info = self.mods, self.info
-        if not hasattr(self, "getters"):
-            self._getters()
-        if self.__dict__.get("fast") is not None and self._unchanged():
-            return self.fast
-        stale = [i for i in range(len(mods)) if not self.valid(i)]
-        if stale:
-            for i in stale:
-                info[i] = self.classify(mods[i], self.prefixes[i])
-            self._getters()
-            with self.pool_lock:
-                self.pool.clear()
-        fast = self.__dict__.get("fast")
-        if fast is None or stale:
-            fast = self.fast = [self._fast(x) for x in info]
-            self.plain = [tuple(k for k in m.__dict__ if k not in _MODULE_TABLES and k not in set(f[5] + f[9] + f[10]))
-                          for m, f in zip(mods, fast)]
-            self._flat_tables()
-        return fast
-
-    def _flat_tables(self):
-        """The per-call checks and the refresh as C-level maps over the whole tree (a Python loop over a
-        ResNet-50's 132 modules and their ~1,600 hook containers cost more than the decode itself)."""
-        dicts = self.t_dicts = [m.__dict__ for m in self.mods]
-        self.t_dlens = list(map(len, dicts))
-        self.t_tables = list(chain.from_iterable(map(_TABLES3, dicts)))
-        self.t_sizes = list(map(len, self.t_tables))
-        self.t_fresh = [d[k] for d, x in zip(dicts, self.info) for k, _ in x[1]]  # the template's empty containers
-        self.t_typed = [(d, k, tv) for d, x in zip(dicts, self.info) for k, tv in x[3] + x[2]]
-        self.p_src = [d for d, keys in zip(dicts, self.plain) for _ in keys]
-        self.p_keys = [k for keys in self.plain for k in keys]
-        self.p_mod = [i for i, keys in enumerate(self.plain) for _ in keys]
-        self.special = [i for i, f in enumerate(self.fast) if f[9] or f[10]]
-
-    def _unchanged(self):
-        """Every template module as classified: __dict__ and table sizes, the same table objects, its fresh
-        containers still empty (a hook registered later must be deep-copied), its special attributes' types."""
-        dicts = self.t_dicts
-        if list(map(len, dicts)) != self.t_dlens or any(self.t_fresh):
-            return False
-        tabs = list(chain.from_iterable(map(_TABLES3, dicts)))
-        if not all(map(is_, tabs, self.t_tables)) or list(map(len, tabs)) != self.t_sizes:
-            return False
-        return all(type(d.get(k)) is tv for d, k, tv in self.t_typed)
-
-    def tree_unchanged(self):
-        """The template's module tree is still the one this recipe walked: every child slot holds the same
-        module object (a replaced submodule — model.head = nn.Linear(...) — needs a new recipe)."""
-        kids = self.__dict__.get("t_kids")
-        if kids is None:
-            self.t_kid_dicts = [m._modules for m in self.mods if m._modules]
-            kids = self.t_kids = [tuple(d.values()) for d in self.t_kid_dicts]
-        return list(map(tuple, map(dict.values, self.t_kid_dicts))) == kids
-
-    def build(self, state):
-        return self._build(state)[0]
-
-    def _build(self, state):
-        """The new module tree: the list of new module objects in recipe order (root first)."""
-        mods = self.mods
-        fast = self._current()
-        new = [m.__class__.__new__(m.__class__) for m in mods]
-        get = state.get
-        deep_todo = []
-        for i, m in enumerate(mods):
-            pnames, pkeys, prgs, bnames, bkeys, fkeys, ftypes, cnames, cidx, tens, deep = fast[i]
-            ts = list(map(get, pkeys))
-            if any(map(is_, ts, repeat(None))):  # a parameter the state lacks (or a None slot): the template's, cloned
-                src = m._parameters
-                ts = [t if t is not None else (None if src[n] is None else src[n].detach().clone())
-                      for n, t in zip(pnames, ts)]
-                P = {n: None if t is None else _make_param(nn.Parameter, t, rg) for n, t, rg in zip(pnames, ts, prgs)}
-            else:
-                P = dict(zip(pnames, map(_make_param, repeat(nn.Parameter), ts, prgs)))
-            B = dict(zip(bnames, map(get, bkeys)))
-            if any(map(is_, B.values(), repeat(None))):
-                srcb = m._buffers
-                B = {n: (t if t is not None else (None if srcb[n] is None else srcb[n].clone())) for n, t in B.items()}
-            d = m.__dict__.copy()  # plain attributes shared (read now: e.g. `training` follows the template)
-            if fkeys:
-                d.update(zip(fkeys, [tv() for tv in ftypes]))
-            for k in tens:
-                d[k] = d[k].clone()
-            d["_parameters"] = P
-            d["_buffers"] = B
-            d["_modules"] = dict(zip(cnames, [None if j is None else new[j] for j in cidx]))
-            new[i].__dict__.update(d)  # (a fresh object's dict: no Module.__setattr__ on the way)
-            if deep:
-                deep_todo.append((i, deep))
-        if deep_todo:  # after every clone is filled in, so the memo maps every module / tensor
-            memo = self._memo(new, state)
-            for i, deep in deep_todo:
-                nd = new[i].__dict__
-                for k in deep:
-                    nd[k] = copy.deepcopy(nd[k], memo)
-        return new
-
-    # -- recycling of decoded modules (UpdateCodec.decode_module) ------------------------------------------
-    POOL_MAX = 64            # skeletons kept per template (a server needs two rounds' uploads: 2 x clients)
-    POOL_BYTES = 16 << 30    # ... and at most this many bytes of decoded storage
-    POOL_FRACTION = 8        # ... nor more than 1/8 of the device's memory
-    EVICT_SLACK = 16         # a tree not handed out for 2 x pool size + this many calls is dropped from the pool
-
-    def pool_limit(self, device):
-        lim = self.__dict__.get("_pool_limit")
-        if lim is None or lim[0] != device:
-            total = None
-            if device is not None and device.type == "cuda":
-                total = torch.cuda.get_device_properties(device).total_memory
-            lim = self._pool_limit = (device, self.POOL_BYTES if total is None else
-                                      min(self.POOL_BYTES, total // self.POOL_FRACTION))
-        return lim[1]
-
-    def build_and_adopt(self, box, D, flat, raws, raw, device, adopt=True):
-        """Build the module tree for the decoded state in box (a one-element list, emptied here: the caller
-        keeps no reference to the state) and keep it in the pool as a skeleton for later decodes of the same
-        layout (unless adopt is False). Returns the root module."""
-        state = box.pop()
-        new = self._build(state)
-        del state
-        root = new[0]
-        if (not adopt or (flat is None and not raws) or not isinstance(raw, RawState)
-                or len(self.pool) >= self.POOL_MAX):
-            return root
-        nbytes = (flat.numel() * 4 if flat is not None else 0) + sum(r.numel() * r.element_size() for r in raws or ())
-        limit = self.pool_limit(device)
-        stream = torch.cuda.current_stream(device) if device is not None and device.type == "cuda" else None
-        with self.pool_lock:
-            if sum(sk.nbytes for sk in self.pool) + nbytes > limit or len(self.pool) >= self.POOL_MAX:
-                return root
-            sk = _Skeleton(root, new, flat, list(raws or ()), D, raw.signature(), device, nbytes)
-            sk.adopt(self)
-            sk.stream, sk.last = stream, self.tick
-            del new
-            sk.base = sk.counts()
-            sk.base[0][0] -= 1  # the root: this frame's `root` is the only transient reference
-            self.pool.append(sk)
-        return root
-
-    def idle_skeleton(self, D, raw, device):
-        """A pooled skeleton of this layout that nothing outside the pool references any more (every module,
-        parameter and buffer object at its idle reference count, the decoded storage at its idle use count,
-        every module's tables unchanged) and its root — (None, None) if there is none. The root is taken
-        while the pool lock is held, so the moment a tree is chosen it is no longer idle for any other
-        thread (the remote server decodes from one thread per upload, coala/server/service.py:74).
-        Idle trees not handed out for a while (2 x the pool size + EVICT_SLACK calls: more than a round needs)
-        are dropped from the pool; held ones stay."""
-        if not self.pool or not isinstance(raw, RawState):
-            return None, None
-        self._current()
-        sig = raw.signature()
-        with self.pool_lock:
-            self.tick += 1
-            found = root = None
-            for sk in self.pool:
-                if sk.D is D and sk.device == device and sk.raw_sig == sig and sk.counts() == sk.base:
-                    found, root = sk, sk.root
-                    sk.generation += 1
-                    sk.last = self.tick
-                    break
-            # only IDLE trees go: a tree still held (a server keeps round r's uploads until round r + 1 replaces them,
-            # coala/server/base.py:377-381) becomes reusable when its holder lets go, however long that takes
-            horizon = 2 * len(self.pool) + self.EVICT_SLACK
-            if any(self.tick - sk.last > horizon for sk in self.pool):
-                self.pool[:] = [sk for sk in self.pool
-                                if self.tick - sk.last <= horizon or sk is found or sk.counts() != sk.base]
-            return found, root
-
-    def refresh(self, sk):
-        """Bring a recycled tree's attributes in line with the template's CURRENT ones, as a fresh build would:
-        plain attributes copied, hook containers emptied if a previous holder registered hooks, special
-        attributes re-copied unless still equal."""
-        memo = None
-        list(map(dict.__setitem__, sk.p_dst, self.p_keys, map(dict.__getitem__, self.p_src, self.p_keys)))
-        if any(sk.fresh):  # a previous holder registered hooks on the recycled tree: empty containers again
-            for i, c in enumerate(sk.mods):
-                nd, f = c.__dict__, self.fast[i]
-                for k, tv in zip(f[5], f[6]):
-                    if nd.get(k):
-                        nd[k] = tv()
-            sk.adopt(self)
-        for i in self.special:
-            m, c = self.mods[i], sk.mods[i]
-            d, nd = m.__dict__, c.__dict__
-            f = self.fast[i]
-            for k in f[9]:
-                nd[k] = d[k].clone()
-            for k in f[10]:
-                try:
-                    same = bool(nd.get(k) == d[k])
-                except Exception:
-                    same = False
-                if not same:
-                    if memo is None:
-                        memo = self._memo(sk.mods, {})
-                    nd[k] = copy.deepcopy(d[k], memo)
-
-    @staticmethod
-    def _fast(x):
-        _, fresh, deep, tens, params, buffers, children = x
-        return (tuple(n for n, _, _ in params), tuple(k for _, k, _ in params), tuple(rg for _, _, rg in params),
-                tuple(n for n, _ in buffers), tuple(k for _, k in buffers),
-                tuple(k for k, _ in fresh), tuple(tv for _, tv in fresh),
-                tuple(n for n, _ in children), tuple(j for _, j in children),
-                tuple(k for k, _ in tens), tuple(k for k, _ in deep))
-
-    def _memo(self, new, state=None):
-        """deepcopy memo: template module / parameter / buffer -> its counterpart in the clone."""
-        memo = {}
-        for m, c in zip(self.mods, new):
-            memo[id(m)] = c
-        for m, c, p in zip(self.mods, new, self.prefixes):
-            for name, t in m._parameters.items():
-                if t is not None and name in c.__dict__.get("_parameters", {}):
-                    memo[id(t)] = c._parameters[name]
-            for name, t in m._buffers.items():
-                if t is not None and name in c.__dict__.get("_buffers", {}):
-                    memo[id(t)] = c._buffers[name]
-        return memo
-
-
-class _Skeleton:
-    """A decoded module tree kept for reuse: its objects (modules, then their parameter / buffer tensors), the
-    decoded storage they view (the flat fp32 decode output and the passthrough groups) and their idle
-    reference counts."""
-
-    __slots__ = ("root", "mods", "objs", "dicts", "dlens", "tables", "tsizes", "flat", "raws", "D", "raw_sig",
-                 "device", "nbytes", "base", "generation", "p_dst", "fresh", "stream", "last")
-
-    def __init__(self, root, mods, flat, raws, D, raw_sig, device, nbytes):
-        self.root, self.mods = root, mods
-        self.objs = list(mods)
-        for c in mods:
-            self.objs.extend(t for t in c._parameters.values() if t is not None)
-            self.objs.extend(t for t in c._buffers.values() if t is not None)
-        self.dicts = [c.__dict__ for c in mods]
-        self.dlens = list(map(len, self.dicts))
-        self.tables = list(chain.from_iterable(map(_TABLES3, self.dicts)))
-        self.tsizes = list(map(len, self.tables))
-        self.flat, self.raws, self.D, self.raw_sig, self.device, self.nbytes = flat, raws, D, raw_sig, device, nbytes
-        self.generation = 0
-        self.stream, self.last = None, 0
-
-    def adopt(self, recipe):
-        """The recipe's flat refresh tables for this tree: where each plain attribute goes, and the tree's own
-        (empty) hook containers, checked in one pass per recycle."""
-        self.p_dst = [self.dicts[i] for i in recipe.p_mod]
-        self.fresh = [c.__dict__[k] for c, f in zip(self.mods, recipe.fast) for k in f[5]]
-
-    def counts(self):
-        """Idle fingerprint: every object's reference count, the decoded storage's use counts, and whether every
-        module still has its attribute count and its very table objects at their sizes (an attribute added or a
-        table replaced by a previous holder keeps the tree from being recycled)."""
-        refs = list(map(sys.getrefcount, self.objs))
-        store = [torch._C._storage_Use_Count(t.untyped_storage()._cdata) for t in [self.flat] + self.raws
-                 if t is not None]
-        tabs = list(chain.from_iterable(map(_TABLES3, self.dicts)))
-        same = (list(map(len, self.dicts)) == self.dlens and all(map(is_, tabs, self.tables))
-                and list(map(len, tabs)) == self.tsizes)
-        return [refs, store, same]
-
-
-_RECIPES = {}  # id(template) -> (weakref to it, recipe)
-_RECIPES_LOCK = threading.Lock()
-
-
-def _recipe(template):
-    """The template's _TreeRecipe (one per template object: the server's global model, for a whole task)."""
-    key = id(template)
-    with _RECIPES_LOCK:
-        hit = _RECIPES.get(key)
-        if hit is None or hit[0]() is not template or not hit[1].tree_unchanged():
-            import weakref
-            hit = (weakref.ref(template), _TreeRecipe(template))
-            _RECIPES[key] = hit
-            if len(_RECIPES) > 32:
-                for k in [k for k, (r, _) in _RECIPES.items() if r() is None]:
-                    del _RECIPES[k]
-    return hit[1]
-
-
-def release_decode_pool():
-    """Drop every template's pooled decoded modules (UpdateCodec.release_pool)."""
-    with _RECIPES_LOCK:
-        recipes = [r for _, r in _RECIPES.values()]
-    for r in recipes:
-        with r.pool_lock:
-            r.pool.clear()
-
-
-def _reuse_after(sk, stream, caller):
-    """Order a recycled tree's rewrite after its previous holder's work and retire stale autograd state.
-    `stream` (None on the CPU) is where the rewrite runs, `caller` the caller's current stream (the stream
-    the module is handed out on). The host reference counts that made the tree idle do not see GPU work:
-    the rewrite waits for everything enqueued so far on the stream the tree was last handed out on (where
-    its holder's work ran, unless the holder moved it to another stream itself — torch's own contract for
-    that is Tensor.record_stream, which a recycled tree cannot honour: pass recycle=False then). The decode
-    kernel writes through raw pointers, so the storage's version counter is bumped here: an autograd graph
-    that saved the previous values raises in backward instead of using the new ones."""
-    if stream is not None and sk.stream is not None and sk.stream != stream and sk.stream != caller:
-        stream.wait_stream(sk.stream)  # (the rewrite's stream already waits for the caller's)
-    sk.stream = caller
-    torch._C._increment_version([t for t in [sk.flat] + sk.raws if t is not None])
-
-
-def module_with_state(template, state):
-    """A new nn.Module shaped like `template` whose parameters / buffers ARE the tensors of `state`
-    (views into the decode output: no parameter data is copied; `template` is never aliased).
-
-    The module tree is rebuilt from a per-template recipe (_TreeRecipe) — new objects of the same classes,
-    their __dict__ copied one level deep with fresh tables and hook dicts, other attributes deep-copied —
-    instead of copy.deepcopy, whose generic recursion cost ~8 ms per ResNet-50 on the server's per-upload
-    path. Tensors outside the state (non-persistent buffers, unregistered tensors) are cloned."""
-    return _recipe(template).build(state)
-
-
-_SAME_LAYOUT = OrderedDict()  # (id(a), id(b)) -> (a, b): pairs of entry lists already found equal
-
-
-def _check_same_layout(entries, base_entries):
-    key = (id(entries), id(base_entries))
-    hit = _SAME_LAYOUT.get(key)
-    if hit is not None and hit[0] is entries and hit[1] is base_entries:
-        return
-    a = [(e["name"], e["dtype"], tuple(e["shape"])) for e in entries]
-    b = [(e["name"], e["dtype"], tuple(e["shape"])) for e in base_entries]
-    if a != b:
-        raise ValueError("update and base model have different state_dict layouts")
-    with _LAYOUTS_LOCK:  # (the header entries are never mutated: the pair stays equal)
-        _SAME_LAYOUT[key] = (entries, base_entries)
-        while len(_SAME_LAYOUT) > 64:
-            _SAME_LAYOUT.popitem(last=False)
-
-
-class _DecodeLayout:
-    """Per header-entries list: the state names, the fp32 segment sizes and where segments / raw entries sit."""
-
-    def __init__(self, entries):
-        self.names = tuple(e["name"] for e in entries)
-        self.sizes = tuple(e["n"] for e in entries if e["kind"] == "seg")
-        self.seg_pos = [i for i, e in enumerate(entries) if e["kind"] == "seg"]
-        self.raw = [(i, e["name"]) for i, e in enumerate(entries) if e["kind"] != "seg"]
-
-
-_DECODE_LAYOUTS = OrderedDict()  # id(entries) -> (entries, _DecodeLayout)
-
-
-def _decode_layout(entries):
-    hit = _DECODE_LAYOUTS.get(id(entries))
-    if hit is not None and hit[0] is entries:
-        return hit[1]
-    D = _DecodeLayout(entries)
-    with _LAYOUTS_LOCK:
-        _DECODE_LAYOUTS[id(entries)] = (entries, D)
-        while len(_DECODE_LAYOUTS) > 64:
-            _DECODE_LAYOUTS.popitem(last=False)
-    return D
-
-
-def as_numpy(t):
-    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)

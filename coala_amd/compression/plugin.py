@@ -59,8 +59,9 @@ import threading
 
 from torch import nn
 
-from .codec import CompressedUpdate, UpdateCodec, _layout_walk, _module_walk
+from .codec import CompressedUpdate, UpdateCodec
 from .download import CompressedModel, compress_model
+from .state import _layout_walk, _module_walk
 
 DATA_TYPE_FEATURE = 2  # coala/pb/common.proto: DataType.DATA_TYPE_FEATURE (protos/coala/pb/common.proto:26)
 FEATURE_CONTENT = "feature_label"  # application/splitFL/client/base_sfl.py:252

@@ -311,7 +311,7 @@ def test_fused_aggregate_recycles_idle_output_modules(cuda):
     result is aggregated into again (the pool does not grow), a held one is never overwritten, and every
     result equals decompress-each + federated_averaging (coala/server/strategies.py:6-29) on the GPU."""
     from coala_amd.compression import UpdateCodec
-    from coala_amd.compression.codec import _recipe
+    from coala_amd.compression.clone import _recipe
     from coala_amd.fl import federated_averaging as fedavg
     dev = torch.device("cuda", 0)
     codec = UpdateCodec(0.02, 8, "delta")

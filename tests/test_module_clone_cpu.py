@@ -192,7 +192,7 @@ def test_recycling_survives_a_template_change():
 def test_layout_reused_only_while_tensors_and_storage_are_unchanged():
     """describe_tensors keeps the layout of the last call while the same tensor objects sit at the same storage;
     a parameter whose .data is swapped for another shape (new storage) or a replaced parameter object is seen."""
-    from coala_amd.compression.codec import _module_walk, describe_tensors
+    from coala_amd.compression.state import _module_walk, describe_tensors
     m = Net()
     names, ts, w = _module_walk(m)
     L1 = describe_tensors(names, ts, w)[0]
@@ -243,7 +243,7 @@ def test_recycler_hands_one_idle_module_to_one_thread_only(monkeypatch):
     barrier injected right after idle_skeleton returns forces both threads through the window between the
     idle check and the caller taking the tree."""
     import threading
-    from coala_amd.compression.codec import _TreeRecipe
+    from coala_amd.compression.clone import _TreeRecipe
     codec, g, base, ups, fresh = _codec_round(seed_global=3)
     m = codec.decode_module(ups[0], g, base=base)
     del m  # one idle tree in the pool
@@ -304,7 +304,7 @@ def test_recycling_with_more_clients_per_round_than_half_the_pool():
     j replaces client j's module of the previous round (coala/server/base.py:377-381), so the trees of round r stay held
     while round r + 1 decodes. From the third round on every decode reuses a pooled tree (none is evicted while held,
     none built anew beyond the pool's capacity), and every module holds its own update."""
-    from coala_amd.compression.codec import _TreeRecipe, _recipe
+    from coala_amd.compression.clone import _TreeRecipe, _recipe
     codec, g, base, ups, fresh = _codec_round(seed_global=7)
     C = _TreeRecipe.POOL_MAX // 2 + 8
     held, seen, built = {}, set(), []
@@ -326,7 +326,7 @@ def test_pool_release_eviction_and_opt_out():
     """release_pool() empties the pool; trees not handed out for a while are evicted; recycle=False never
     pools or reuses a module."""
     from coala_amd.compression import UpdateCodec
-    from coala_amd.compression.codec import _TreeRecipe, _recipe
+    from coala_amd.compression.clone import _TreeRecipe, _recipe
     from tests.oracle_backend import OracleBackend
     codec, g, base, ups, fresh = _codec_round(seed_global=5)
     ms = [codec.decode_module(u, g, base=base) for u in ups]

@@ -23,7 +23,7 @@ def main():
     base = codec.snapshot(g)
     up = codec.encode_module(m, base=base)
     torch.cuda.synchronize()
-    from coala_amd.compression.codec import _layout_walk, _module_walk
+    from coala_amd.compression.state import _layout_walk, _module_walk
     names, tensors, walk = _module_walk(m)
     d, segs = _layout_walk(names, tensors, walk)
     plan = codec.plan_for(d.L.sizes_key, dev)

@@ -17,6 +17,7 @@ import torch  # noqa: E402
 
 from coala_amd.compression import UpdateCodec  # noqa: E402
 from coala_amd.compression import codec as C  # noqa: E402
+from coala_amd.compression import state as S  # noqa: E402
 from coala_amd.layouts import build_module  # noqa: E402
 
 
@@ -46,8 +47,8 @@ def main(steps=50):
         up = codec.encode_module(m, base=base)
         codec.decode_module(up, g, base=base)
     torch.cuda.synchronize()
-    names, ts, walk = C._module_walk(m)
-    d, segs = C._layout_walk(names, ts, walk)
+    names, ts, walk = S._module_walk(m)
+    d, segs = S._layout_walk(names, ts, walk)
     L, ptrs = d.L, d.seg_ptrs
     plan = codec.plan_for(L.sizes_key, dev)
     ws = codec._workspace(plan)
@@ -58,9 +59,9 @@ def main(steps=50):
         ("  describe_tensors (layout + raw snapshot)", lambda: C.describe_tensors(names, ts), False),
         ("  state_dict() (what round 2 walked)", lambda: m.state_dict(), False),
         ("  host: encode_module returns", lambda: codec.encode_module(m, base=base), "host"),
-        ("  host: _module_walk", lambda: C._module_walk(m), "host"),
-        ("  host: _layout_walk", lambda: C._layout_walk(names, ts, walk), "host"),
-        ("  host: _raw_snapshot (gather launch)", lambda: C._raw_snapshot(d, ts, codec.backend.gather_scalars),
+        ("  host: _module_walk", lambda: S._module_walk(m), "host"),
+        ("  host: _layout_walk", lambda: S._layout_walk(names, ts, walk), "host"),
+        ("  host: _raw_snapshot (gather launch)", lambda: S._raw_snapshot(d, ts, codec.backend.gather_scalars),
          "host"),
         ("  host: plan.encode_segments", lambda: plan.encode_segments(segs, base=base.flat, workspace=ws,
                                                                       checked=True, ptrs=ptrs), "host"),
