@@ -50,6 +50,12 @@ SIGNATURES = [
     ("coalac_plan_packed_bytes", _I, [_P, ctypes.POINTER(_U64)]),
     ("coalac_pack", _I, [_P, _P, _P, _P, _U64, _P]),
     ("coalac_unpack", _I, [_P, _P, _U64, _P, _P, _P, _P]),
+    # bit-packed dense codes: plan, bytes / plan, vals, packed, packed_bytes, stream / plan, packed, packed_bytes, vals,
+    # stream / plan, packed, packed_bytes, mn, scale, base, out, stream
+    ("coalac_plan_dense_packed_bytes", _I, [_P, ctypes.POINTER(_U64)]),
+    ("coalac_pack_dense", _I, [_P, _P, _P, _U64, _P]),
+    ("coalac_unpack_dense", _I, [_P, _P, _U64, _P, _P]),
+    ("coalac_decode_packed", _I, [_P, _P, _U64, _P, _P, _P, _P, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -61,7 +67,7 @@ SIGNATURES = [
     ("coalac_debug_brackets", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _I]),
 ]
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class CodecError(RuntimeError):

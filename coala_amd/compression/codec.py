@@ -120,14 +120,28 @@ class CompressedUpdate:
 
     @property
     def packed(self):
-        """A compact carrier's packed entry stream (wire.py, version 3) as a uint32 tensor, else None. Packed on the
-        GPU right after the encode where the plan can (CodecPlan.pack); otherwise on the host, on first use."""
+        """A compact carrier's packed entry stream (wire.py, version 3), or a dense-packed carrier's bit-packed code
+        stream (version 4), as a uint32 tensor; else None. Packed on the GPU right after the encode where the plan can
+        (CodecPlan.pack / pack_dense); otherwise on the host, on first use (a received carrier: its blob's section)."""
+        if self.header.get("dense_packed"):
+            if self._packed[0] is None:
+                blob = self._blob[0]
+                if blob is not None:
+                    o, n = wire.sections(blob, self.header)[1]["packed"]
+                    words = np.frombuffer(blob, dtype="<u4", count=n // 4, offset=o).copy()
+                else:
+                    words = wire.pack_dense_codes(_to_host(self.encoded.vals)[0], self._seg_sizes(), self.header["bits"])
+                self._packed[0] = torch.from_numpy(words)
+            return self._packed[0]
         if not self.header.get("compact"):
             return None
         if self._packed[0] is None:
             idx, vals = _to_host(self.encoded.idx, self.encoded.vals)
             self._packed[0] = torch.from_numpy(wire.pack_entries(idx, vals, self.header["bits"]))
         return self._packed[0]
+
+    def _seg_sizes(self):
+        return _decode_layout(self.header["entries"]).sizes
 
     # -- size accounting (client/base.py:155, 474-487) -------------------------------------------
     @property
@@ -136,6 +150,8 @@ class CompressedUpdate:
         vb = 4 if h["bits"] == RAW_BITS else 1
         ib = 0 if h["ratio"] >= 1.0 else 4  # ratio 1: indices implied, not shipped (wire.py "dense")
         raw_b = _raw_nbytes(self.raw)
+        if h.get("dense_packed"):  # mn, scale and the bit-packed code stream
+            return 8 * h["n_segments"] + 4 * wire.dense_packed_words(self._seg_sizes(), h["bits"]) + raw_b
         if h.get("compact"):  # the packed stream, and the values only as fp32
             return (8 * h["n_segments"] + 4 * wire.packed_words(h["total_k"], h["bits"])
                     + (4 * h["total_k"] if h["bits"] == RAW_BITS else 0) + 4 * h["n_units"] + raw_b)
@@ -171,9 +187,13 @@ class CompressedUpdate:
         # the header (with each raw entry's blob offset) depends on the layout and the raw byte counts only
         hjson = _PACKED_HEADERS.get(h["entries"], (h["ratio"], h["bits"], h["mode"], h["n_segments"], h.get("total_k"),
                                                    h.get("n_units"), tuple(map(len, rawb.values())),
-                                                   bool(h.get("compact"))), header_json)
+                                                   bool(h.get("compact")), bool(h.get("dense_packed"))), header_json)
         enc = self.encoded
         rawbytes = b"".join(rawb[e["name"]] for e in h["entries"] if e["kind"] == "raw")
+        if h.get("dense_packed"):  # wire v4: the bit-packed stream instead of the uint8 codes, which are not copied
+            arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device))
+            return wire.pack({"dense": True, "dense_packed": True}, arrs[0], arrs[1], None, None, rawbytes,
+                             header_json=hjson, packed=arrs[2])
         if h.get("compact"):  # wire v3: the packed stream instead of idx and the uint8 codes, neither copied
             f32 = h["bits"] == RAW_BITS
             arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device), enc.ustart, *((enc.vals,) if f32 else ()))
@@ -192,10 +212,14 @@ class CompressedUpdate:
         idx / vals region through `staging` (a pinned host buffer: staging(nbytes) -> uint8 tensor), so
         the copy is asynchronous on the caller's stream; device tensors are typed views into it. A compact
         blob's region (mn ... ustart) holds the packed stream: idx / vals are then materialised on the device by
-        `plan`.unpack (the decoding plan of this update; without one, the host-unpacked buffers are copied)."""
+        `plan`.unpack (the decoding plan of this update; without one, the host-unpacked buffers are copied). A
+        dense-packed blob (wire v4) for a plan that decodes the stream (decode_packed): its mn ... packed region, the
+        stream staying packed on the device (_dense_packed_to)."""
         device = torch.device(device)
         blob = self._blob[0]
         compact = bool(self.header.get("compact"))
+        if self.header.get("dense_packed") and device.type == "cuda" and getattr(plan, "decode_packed", None) is not None:
+            return self._dense_packed_to(device, staging)
         if (staging is None or device.type != "cuda" or blob is None or self.header.get("dense")
                 or self.encoded.idx.device == device or (compact and getattr(plan, "unpack", None) is None)):
             return self.encoded.to(device, non_blocking=True)
@@ -223,6 +247,30 @@ class CompressedUpdate:
             return Encoded(idx, vals, view("mn", torch.float32), view("scale", torch.float32), ustart)
         return Encoded(view("idx", torch.int32), view("vals", vdt), view("mn", torch.float32),
                        view("scale", torch.float32), view("ustart", torch.int32) if "ustart" in sec else None)
+
+    def _dense_packed_to(self, device, staging):
+        """encoded_to of a dense-packed carrier for a plan that reads the stream: an Encoded whose `packed` is the
+        bit-packed stream on `device`. A received carrier moves ONE pinned host-to-device copy of its blob's mn ...
+        packed region and has no uint8 codes there (vals None: CodecPlan.unpack_dense makes them for who needs them);
+        a carrier whose buffers are on the device already is handed out as it is."""
+        enc, blob = self.encoded, self._blob[0]
+        if enc.mn.device == device:
+            return Encoded(enc.idx, enc.vals, enc.mn, enc.scale, None, self.packed.to(device, non_blocking=True))
+        if blob is None or staging is None:
+            return Encoded(torch.empty(0, dtype=torch.int32, device=device), None, enc.mn.to(device, non_blocking=True),
+                           enc.scale.to(device, non_blocking=True), None, self.packed.to(device, non_blocking=True))
+        _, sec = wire.sections(blob, self.header)
+        lo, hi = sec["mn"][0], sec["packed"][0] + sec["packed"][1]
+        stage = staging(hi - lo)
+        stage[:hi - lo].numpy()[:] = np.frombuffer(blob, dtype=np.uint8, count=hi - lo, offset=lo)
+        dev = torch.empty(hi - lo, dtype=torch.uint8, device=device)
+        dev.copy_(stage[:hi - lo], non_blocking=True)
+
+        def view(name, dt):
+            o, n = sec[name]
+            return dev[o - lo:o - lo + n].view(dt)
+        return Encoded(torch.empty(0, dtype=torch.int32, device=device), None, view("mn", torch.float32),
+                       view("scale", torch.float32), None, view("packed", torch.uint32))
 
     @classmethod
     def from_bytes(cls, blob):
@@ -296,9 +344,13 @@ class UpdateCodec:
                (12 + bits)-bit field instead of an int32 index and a whole uint8 code — 2.5 bytes per entry at 8 bits,
                2 at 4 bits, instead of 5. Lossless (the decoded result is bit-identical) and self-describing (a decoder
                needs no switch). A dense plan or ratio 1 keeps the dense format. Off by default.
+        pack_dense: ratio-1 (dense) updates with bits below 8 travel with their codes bit-packed (wire v4, DESIGN.md
+               §13): `bits` bits per element instead of a whole byte — the download direction's payload, or a
+               pure-quantisation upload. Lossless and self-describing, as compact is. At bits 8 or 32, or below ratio
+               1, the payload is what it is without the option. Off by default.
     """
 
-    def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True, compact=False):
+    def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True, compact=False, pack_dense=False):
         if not (0.0 < float(ratio) <= 1.0):
             raise ValueError(f"ratio must be in (0, 1], got {ratio}")
         if bits not in VALID_BITS:
@@ -308,6 +360,7 @@ class UpdateCodec:
         self.ratio, self.bits, self.mode = float(ratio), int(bits), mode
         self.recycle = bool(recycle)
         self.compact = bool(compact)
+        self.pack_dense = bool(pack_dense)
         self.backend = backend if backend is not None else HipBackend()
         self._plans = {}
         self._plan_fast = IdentityCache(32)  # (sizes object; ratio, bits, clients, device) -> plan
@@ -454,6 +507,13 @@ class UpdateCodec:
             pack = getattr(plan, "pack", None)
             if pack is not None and enc.idx.device.type == "cuda":
                 packed = pack(enc, stream=cur)
+        elif self.pack_dense and self.ratio >= 1.0 and self.bits < 8 and _all_kept(plan):
+            # wire v4: the dense codes bit-packed on the encode's stream, directly after it (and after the error
+            # feedback's commit, which reads the uint8 codes); a plan without pack_dense packs on the host, as above
+            header["dense_packed"] = True
+            pack = getattr(plan, "pack_dense", None)
+            if pack is not None and enc.vals.device.type == "cuda":
+                packed = pack(enc, stream=cur)
         return CompressedUpdate(header, enc, raw() if callable(raw) else raw, packed=packed)
 
     def _thread_stream(self, device):
@@ -566,7 +626,10 @@ class UpdateCodec:
                 with torch.cuda.stream(side):
                     enc = update.encoded_to(device, staging=self._staging, plan=plan)
                     self._staged(side)
-                    flat = plan.decode(enc, base=base_flat, out=out, stream=side)
+                    if enc.packed is not None:  # a dense-packed update: decoded from the bit stream itself
+                        flat = plan.decode_packed(enc.packed, enc.mn, enc.scale, base=base_flat, out=out, stream=side)
+                    else:
+                        flat = plan.decode(enc, base=base_flat, out=out, stream=side)
                     if into is not None:
                         _copy_raw_groups(raw, into, non_blocking=True)
                 cur.wait_stream(side)
@@ -647,8 +710,9 @@ class UpdateCodec:
         h0 = updates[0].header
         for u in updates[1:]:
             h = u.header
-            if (h["ratio"], h["bits"], h["mode"], h["entries"], bool(h.get("compact"))) != \
-                    (h0["ratio"], h0["bits"], h0["mode"], h0["entries"], bool(h0.get("compact"))):
+            if (h["ratio"], h["bits"], h["mode"], h["entries"], bool(h.get("compact")), bool(h.get("dense_packed"))) != \
+                    (h0["ratio"], h0["bits"], h0["mode"], h0["entries"], bool(h0.get("compact")),
+                     bool(h0.get("dense_packed"))):
                 raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode / payload format")
         sizes = [e["n"] for e in h0["entries"] if e["kind"] == "seg"]
         device = self.backend.default_device() if device is None else torch.device(device)
@@ -676,7 +740,18 @@ class UpdateCodec:
         if sizes:
             C = len(updates)
             plan = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"], clients=C)
-            encs = [u.encoded.to(device, non_blocking=True) for u in updates]
+            one = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"]) if h0.get("dense_packed") else None
+            unpack = getattr(one, "unpack_dense", None)
+
+            def on_device(u):
+                e = u.encoded
+                if unpack is None or e.vals.device == device:
+                    return e.to(device, non_blocking=True)
+                # a dense-packed upload whose codes are not on the device: the bit stream is moved instead, and the
+                # codes the kernel reads are unpacked there
+                return Encoded(e.idx.to(device), unpack(u.packed.to(device, non_blocking=True)),
+                               e.mn.to(device, non_blocking=True), e.scale.to(device, non_blocking=True), None)
+            encs = [on_device(u) for u in updates]
             batched = Encoded(*(torch.cat([getattr(e, f) for e in encs]) for f in ("idx", "vals", "mn", "scale")),
                               torch.cat([e.ustart for e in encs]) if all(e.ustart is not None for e in encs) else None)
             avg_mask = None

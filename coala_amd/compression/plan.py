@@ -19,18 +19,22 @@ from .spec import RAW_BITS, UNIT, VALID_BITS, SegmentTable, SubTable
 class Encoded:
     """Device buffers of one encode: idx int32[K], vals uint8[K] (fp32[K] when bits == 32),
     mn fp32[T], scale fp32[T], and (wire v2) ustart int32[U]: per 4096-element unit, the segment-relative
-    index of its first kept entry — a decoder then needs no search of the idx lists (None: not available)."""
+    index of its first kept entry — a decoder then needs no search of the idx lists (None: not available).
+    packed: a dense-packed update's bit-packed code stream (wire v4, uint32[P]) where its holder has it on the
+    buffers' device — CodecPlan.decode_packed reads it instead of vals, which may then be None until
+    CodecPlan.unpack_dense makes the codes (None: the update is not dense-packed, or only its codes are here)."""
     idx: torch.Tensor
     vals: torch.Tensor
     mn: torch.Tensor
     scale: torch.Tensor
     ustart: torch.Tensor = None
+    packed: torch.Tensor = None
 
     FIELDS = ("idx", "vals", "mn", "scale", "ustart")
 
     def to(self, device, non_blocking=False):
         return Encoded(*(None if t is None else t.to(device, non_blocking=non_blocking)
-                         for t in (self.idx, self.vals, self.mn, self.scale, self.ustart)))
+                         for t in (self.idx, self.vals, self.mn, self.scale, self.ustart, self.packed)))
 
 
 def _ptr(t):
@@ -378,6 +382,94 @@ class CodecPlan:
                                          _ptr(idx), _ptr(vals), _stream_handle(stream))
         _lib.check(rc, "coalac_unpack")
         return idx, vals
+
+    # -- bit-packed dense codes (wire v4) ---------------------------------------------------------
+    @property
+    def dense_packed_words(self):
+        """uint32 words of a dense plan's bit-packed code stream: the sum over its segment rows of
+        ceil(n * bits / 32) (wire.dense_packed_words). A sparse plan, or bits 32, has none (ValueError)."""
+        n = self.__dict__.get("_dense_packed_words")
+        if n is None:
+            self._need_dense("dense_packed_words")
+            b = ctypes.c_uint64()
+            _lib.check(self._lib.coalac_plan_dense_packed_bytes(self._h, ctypes.byref(b)),
+                       "coalac_plan_dense_packed_bytes")
+            n = self._dense_packed_words = b.value // 4
+        return n
+
+    def _need_dense(self, who):
+        if not self.dense:
+            raise ValueError(f"{who}: needs a dense plan (every segment keeps all its elements); a sparse plan's "
+                             "payload is packed by pack / unpack")
+        if self.bits == RAW_BITS:
+            raise ValueError(f"{who}: bits 32 has no codes to pack")
+
+    def _check_dense_packed(self, t, name):
+        n = self.dense_packed_words
+        if t.device != self.device or t.dtype != torch.uint32 or not t.is_contiguous() or t.numel() < n:
+            raise ValueError(f"{name}: need a contiguous uint32[{n}] tensor on {self.device}, got "
+                             f"{t.dtype}[{t.numel()}] on {t.device}")
+
+    def _check_codes(self, t, name):
+        if t.device != self.device or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < self.total_k:
+            raise ValueError(f"{name}: need a contiguous uint8[{self.total_k}] tensor on {self.device}, got "
+                             f"{t.dtype}[{t.numel()}] on {t.device}")
+        if t.data_ptr() % 4:  # (the kernels take whole dwords where a unit's codes start on one)
+            raise ValueError(f"{name}: storage must be 4-byte aligned")
+
+    def pack_dense(self, enc, out=None, stream=None):
+        """A dense plan's uint8 codes (enc: an Encoded, or the codes tensor itself) -> the bit-packed stream,
+        uint32[dense_packed_words] (coalac_pack_dense: every code as a `bits`-bit field, each segment's fields from a
+        word boundary on). Asynchronous on `stream`."""
+        self._need_dense("pack_dense")
+        vals = enc.vals if isinstance(enc, Encoded) else enc
+        self._check_codes(vals, "pack_dense codes")
+        with _on(stream):
+            if out is None:
+                out = torch.empty(self.dense_packed_words, dtype=torch.uint32, device=self.device)
+        self._check_dense_packed(out, "packed output")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_pack_dense(self._h, _ptr(vals), _ptr(out), ctypes.c_uint64(4 * out.numel()),
+                                             _stream_handle(stream))
+        _lib.check(rc, "coalac_pack_dense")
+        return out
+
+    def unpack_dense(self, packed, out=None, stream=None):
+        """The bit-packed stream -> the uint8 codes, uint8[total_k] (coalac_unpack_dense); `out`: a buffer to write
+        into — only the positions of the plan's own segments are written. Asynchronous on `stream`."""
+        self._need_dense("unpack_dense")
+        self._check_dense_packed(packed, "packed stream")
+        with _on(stream):
+            if out is None:
+                out = torch.empty(self.total_k, dtype=torch.uint8, device=self.device)
+        self._check_codes(out, "unpack_dense output")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_unpack_dense(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(out),
+                                               _stream_handle(stream))
+        _lib.check(rc, "coalac_unpack_dense")
+        return out
+
+    def decode_packed(self, packed, mn, scale, base=None, out=None, stream=None):
+        """decode() of a dense plan straight from the bit-packed stream (coalac_decode_packed: no byte-per-element
+        intermediate) -> dense flat fp32[span] (+ base, fused); bit-identical to unpack_dense followed by decode.
+        Asynchronous on `stream`."""
+        self._need_dense("decode_packed")
+        self._check_dense_packed(packed, "packed stream")
+        for t in (mn, scale):
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or \
+                    t.numel() < self.n_segments:
+                raise ValueError(f"decode_packed: need mn / scale as float32[{self.n_segments}] on {self.device}, got "
+                                 f"{t.dtype}[{t.numel()}] on {t.device}")
+        self._check_flat(base, "base")
+        with _on(stream):
+            if out is None:
+                out = self.empty_flat() if base is None else torch.empty_like(base)
+        self._check_flat(out, "output")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_decode_packed(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(mn),
+                                                _ptr(scale), _ptr(base), _ptr(out), _stream_handle(stream))
+        _lib.check(rc, "coalac_decode_packed")
+        return out
 
     def unit_starts(self, idx, stream=None):
         """The per-unit starts (wire v2) of this plan's idx list, computed on the device for a payload that carries

@@ -32,6 +32,9 @@ Behaviour:
   * compact payload (opt-in, `codec_compact = True` on the client): a sparse upload ships every kept entry as one
     (12 + bits)-bit field (wire v3) instead of 5 bytes; the blob describes itself, so the server needs
     no switch and decodes it to the same bits. Uploads of mixed formats are decoded one by one, not fused.
+  * bit-packed dense codes (opt-in, `codec_download_pack = True` on the server for the download, `codec_pack_dense =
+    True` on a client for a ratio-1 upload; bits below 8): every code travels as `bits` bits instead of a byte (wire
+    v4). Lossless and self-describing: the receiver has no switch.
   * calculate_model_size(): reports the real payload size for a carrier (base.py:155, 474-487).
   * server decompression(model): CompressedUpdate -> a NEW nn.Module (never aliases self.model, which
     aggregation overwrites, base.py:571) built on the pre-aggregation global model (delta mode: w_global
@@ -105,7 +108,8 @@ class _CodecOwner:
         c = self.__dict__.get("_update_codec")
         if c is None:
             c = UpdateCodec(self.codec_ratio, self.codec_bits, self.codec_mode, self.codec_backend,
-                            recycle=self.codec_recycle, compact=getattr(self, "codec_compact", False))
+                            recycle=self.codec_recycle, compact=getattr(self, "codec_compact", False),
+                            pack_dense=getattr(self, "codec_pack_dense", False))
             self.__dict__["_update_codec"] = c
         return c
 
@@ -126,6 +130,11 @@ class CompressionClientMixin(_CodecOwner):
     # instead of an int32 index and a uint8 code. Lossless; the blob describes itself, so the server has no switch.
     # Off by default: blobs and sizes are then exactly what they were.
     codec_compact = False
+
+    # bit-packed codes for ratio-1 uploads (wire v4): with codec_ratio 1 and codec_bits below 8 every
+    # element travels as codec_bits bits instead of a whole byte. Lossless and self-describing, as codec_compact is.
+    # Off by default; below ratio 1, or at 8 or 32 bits, it changes nothing.
+    codec_pack_dense = False
 
     def reset_error_feedback(self):
         """Zero this client's residual (e.g. when it joins a new task with the same model)."""
@@ -241,11 +250,14 @@ class CompressionServerMixin(_CodecOwner):
     codec_download = False        # compress the distributed global model (download direction)
     codec_download_ratio = 1.0    # dense: indices implied (wire.py "dense")
     codec_download_bits = 8
+    codec_download_pack = False   # bit-pack the download's codes (wire v4): codec_download_bits bits per element
+                                  # instead of a byte, at ratio 1 and fewer than 8 bits; the receiver has no switch
 
     def _download_codec(self):
         c = self.__dict__.get("_download_update_codec")
         if c is None:
-            c = UpdateCodec(self.codec_download_ratio, self.codec_download_bits, "weights", self.codec_backend)
+            c = UpdateCodec(self.codec_download_ratio, self.codec_download_bits, "weights", self.codec_backend,
+                            pack_dense=self.codec_download_pack)
             self.__dict__["_download_update_codec"] = c
         return c
 
@@ -354,8 +366,9 @@ class CompressionServerMixin(_CodecOwner):
                 weights = [1 for _ in models]
             h0 = models[0].header
             if all(m.header["entries"] == h0["entries"] and
-                   (m.header["ratio"], m.header["bits"], m.header["mode"], bool(m.header.get("compact"))) ==
-                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")))
+                   (m.header["ratio"], m.header["bits"], m.header["mode"], bool(m.header.get("compact")),
+                    bool(m.header.get("dense_packed"))) ==
+                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")), bool(h0.get("dense_packed")))
                    for m in models):
                 base = self._global_snapshot() if h0["mode"] == "delta" else None
                 codec = self._codec()

@@ -7,7 +7,8 @@ self-describing because remote clients never receive new config keys (OperateCon
 
 Layout (little-endian):
     0   8B   magic b"COALAQ1\\0"
-    8   u32  format version (3 when the header has "compact", 2 when it has "n_units" only, else 1)
+    8   u32  format version (4 when the header has "dense_packed", 3 when it has "compact", 2 when it has "n_units"
+             only, else 1)
     12  u32  header length H
     16  H    UTF-8 JSON header: ratio, bits, mode, n_segments, total_k, [n_units], entries[]
              entry = {"name", "dtype", "shape", "kind": "seg", "seg": i, "n", "k", "out_off"}
@@ -37,6 +38,22 @@ Version 3, the COMPACT payload (opt-in, sparse uploads only; header key "compact
         idx[j] = (u_s << 12) | (field_j & 0xFFF)      vals[j] = field_j >> 12
     pack_entries / unpack_entries below are this format on the host (numpy); the GPU's k_pack / k_unpack
     (coalac.hip) produce and read the same bytes.
+
+Version 4, BIT-PACKED DENSE CODES (opt-in, "dense" updates with bits 1..7 only; header keys "dense": true and
+"dense_packed": true, no "n_units"):
+         mn f32[T] | scale f32[T] | packed u32[P] | raw bytes
+    With code width b = bits, segment s (in header order) owns W_s = ceil(n_s * b / 32) uint32 words at word offset
+    pw_s = sum of W_t for t < s; the stream is P = sum of W_s words, and an empty segment owns none. Entry e of segment
+    s — the code of its element e — occupies bits [e*b, (e+1)*b) of the segment's sub-stream, a little-endian bit
+    stream as in version 3 (bit t is bit t % 32 of word t // 32). The padding bits of a segment's last word are zero,
+    so equal payloads give equal bytes; a receiver ignores them. Every segment — and so every 4096-element unit of it,
+    unit u_s at word pw_s + 128*b*u_s — starts on a word boundary. Any b-bit field is a legal code (<= 2^b - 1), so an
+    untrusted stream can mis-decode but cannot produce an out-of-range code. At bits 8 the stream would be as long as
+    the codes and at bits 32 there are none: neither is ever packed, and a header that says so is rejected.
+    dense_packed_words / pack_dense_codes / unpack_dense_codes below are this format on the host (numpy); the GPU's
+    k_pack_dense / k_unpack_dense / k_dense_deq_packed (coalac.hip) produce and read the same bytes. unpack() of a
+    version-4 blob returns the rebuilt uint8 codes, so validate() and every consumer of codes sees what it sees for
+    a version-1 / 2 dense blob.
 """
 import json
 import struct
@@ -51,6 +68,7 @@ MAGIC = b"COALAQ1\0"
 VERSION = 1     # mn | scale | idx | vals | raw
 VERSION_2 = 2   # ... | vals | ustart | raw
 VERSION_3 = 3   # mn | scale | packed | [vals f32] | ustart | raw  (header "compact": true)
+VERSION_4 = 4   # mn | scale | packed | raw  (header "dense": true, "dense_packed": true)
 INDEX_BITS = 12  # low index bits in a packed field: log2(UNIT), the position inside the entry's 4096-element unit
 
 
@@ -125,11 +143,109 @@ def unpack_entries(packed, ustart, segs_n, segs_k, bits):
     return idx, vals
 
 
+def _segment_words(sizes, bits):
+    """(W_s per segment, b) of a dense-packed stream; bits must be a code width."""
+    b = int(bits)
+    if not 1 <= b <= 8:
+        raise ValueError(f"COALAQ1: dense codes are packed at 1..8 bits, not {bits}")
+    n = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    if np.any(n < 0):
+        raise ValueError("COALAQ1: bad segment sizes for a dense-packed stream")
+    return (n * b + 31) // 32, b
+
+
+def dense_packed_words(sizes, bits):
+    """uint32 words P of the bit-packed stream of dense segments of `sizes` elements: the sum of ceil(n * bits / 32)."""
+    return int(_segment_words(sizes, bits)[0].sum())
+
+
+def _group_shifts(b):
+    """For each of the 32 entries of a group (b whole words): (word, shift, bits that spill into the next word)."""
+    return [((i * b) >> 5, (i * b) & 31, max(0, ((i * b) & 31) + b - 32)) for i in range(32)]
+
+
+def pack_dense_codes(vals, sizes, bits, out_off=None):
+    """uint8 codes -> the bit-packed dense stream, uint32[dense_packed_words(sizes, bits)]. Segment s holds sizes[s]
+    codes at vals[out_off[s]:] (default: back to back, the running sum of sizes); entry e of it lands at bits
+    [e*b, (e+1)*b) of the segment's own words, which start at word pw_s; padding bits are zero."""
+    W, b = _segment_words(sizes, bits)
+    n = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    off = np.cumsum(n) - n if out_off is None else np.asarray(out_off, dtype=np.int64).reshape(-1)
+    vals = np.asarray(vals).reshape(-1)
+    out = np.zeros(int(W.sum()), dtype="<u4")
+    shifts, mask, pw = _group_shifts(b), np.uint64((1 << b) - 1), 0
+    for ns, ws, o in zip(n.tolist(), W.tolist(), off.tolist()):
+        if not ns:
+            continue
+        if o < 0 or o + ns > vals.size:
+            raise ValueError("COALAQ1: segment codes past the end of vals")
+        G = (ns + 31) // 32  # 32-entry groups = b words each; the last one zero-padded
+        c = np.zeros(G * 32, dtype=np.uint64)
+        c[:ns] = vals[o:o + ns]
+        c = (c & mask).reshape(G, 32)
+        words = np.zeros((G, b + 1), dtype=np.uint64)
+        for i, (wd, sh, spill) in enumerate(shifts):
+            words[:, wd] |= (c[:, i] << np.uint64(sh)) & np.uint64(0xFFFFFFFF)
+            if spill:
+                words[:, wd + 1] |= c[:, i] >> np.uint64(b - spill)
+        out[pw:pw + ws] = words[:, :b].reshape(-1)[:ws].astype("<u4")
+        pw += ws
+    return out
+
+
+def unpack_dense_codes(packed, sizes, bits, out_off=None, out=None):
+    """The bit-packed dense stream -> uint8 codes (the inverse of pack_dense_codes; padding bits are ignored). out: a
+    uint8 array to write into (default: a new one of sum(sizes), or of max(out_off + sizes)); only the segments' own
+    positions are written. A stream shorter than dense_packed_words(sizes, bits) is a ValueError."""
+    W, b = _segment_words(sizes, bits)
+    n = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    off = np.cumsum(n) - n if out_off is None else np.asarray(out_off, dtype=np.int64).reshape(-1)
+    packed = np.ascontiguousarray(packed, dtype="<u4").reshape(-1)
+    if packed.size < int(W.sum()):
+        raise ValueError("COALAQ1: truncated packed section")
+    if out is None:
+        out = np.zeros(int((off + n).max()) if n.size else 0, dtype=np.uint8)
+    shifts, mask, pw = _group_shifts(b), np.uint64((1 << b) - 1), 0
+    for ns, ws, o in zip(n.tolist(), W.tolist(), off.tolist()):
+        if not ns:
+            continue
+        G = (ns + 31) // 32
+        words = np.zeros(G * b + 1, dtype=np.uint64)  # (+ 1: the word after the last, for a field that would spill)
+        words[:ws] = packed[pw:pw + ws]
+        lo, hi = words[:G * b].reshape(G, b), words[1:G * b + 1].reshape(G, b)
+        c = np.empty((G, 32), dtype=np.uint8)
+        for i, (wd, sh, spill) in enumerate(shifts):
+            v = lo[:, wd] >> np.uint64(sh)
+            if spill:
+                v = v | (hi[:, wd] << np.uint64(32 - sh))
+            c[:, i] = (v & mask).astype(np.uint8)
+        out[o:o + ns] = c.reshape(-1)[:ns]
+        pw += ws
+    return out
+
+
+def _seg_sizes(header):
+    return [int(e["n"]) for e in header["entries"] if e["kind"] == "seg"]
+
+
 def pack(header, mn, scale, idx, vals, raw, header_json=None, ustart=None, packed=None):
     """numpy arrays + raw bytes -> blob (bytes). A "dense" header drops idx (it is implied). header_json: the
     header's JSON encoding, if the caller has it already. ustart: the per-unit starts (version 2; the header
     must then carry "n_units" = len(ustart)). packed: the packed entry stream (version 3, which needs ustart and a
-    header with "compact": true): it stands where idx stood, and vals is the fp32 values at bits 32, else None."""
+    header with "compact": true): it stands where idx stood, and vals is the fp32 values at bits 32, else None.
+    A header with "dense" and "dense_packed" (version 4): packed is the bit-packed dense stream, the only section
+    after mn and scale (idx, vals and ustart are not written)."""
+    if header.get("dense_packed"):
+        if not header.get("dense") or packed is None or ustart is not None or "n_units" in header:
+            raise ValueError("COALAQ1: a dense-packed payload needs \"dense\", the packed stream and no per-unit starts")
+        h = header_json if header_json is not None else encode_header(header)
+        parts, size = [MAGIC, struct.pack("<II", VERSION_4, len(h)), h], 16 + len(h)
+        for arr in (np.ascontiguousarray(mn, "<f4"), np.ascontiguousarray(scale, "<f4"), np.ascontiguousarray(packed, "<u4")):
+            b = arr.tobytes()
+            parts += [b"\0" * _pad16(size), b]
+            size += _pad16(size) + len(b)
+        parts += [b"\0" * _pad16(size), bytes(raw)]
+        return b"".join(parts)
     if header.get("dense"):
         idx = np.zeros(0, dtype=np.int32)
     if (ustart is not None) != ("n_units" in header) or (ustart is not None and len(ustart) != header["n_units"]):
@@ -187,8 +303,9 @@ def encode_header(header):
 
 
 def sections(blob, header=None):
-    """(header, {name: (byte offset, byte count)}) of the mn / scale / idx / vals (/ ustart) sections in `blob`,
-    which lie back to back (each 16-byte aligned) — one host-to-device copy moves all of them."""
+    """(header, {name: (byte offset, byte count)}) of the mn / scale / idx / vals (/ ustart) sections in `blob` — a
+    compact or dense-packed blob: `packed` where idx (and the uint8 codes) stood — which lie back to back (each
+    16-byte aligned): one host-to-device copy moves all of them."""
     mv = memoryview(blob)
     if bytes(mv[:8]) != MAGIC:
         raise ValueError("not a COALAQ1 blob (bad magic)")
@@ -200,7 +317,9 @@ def sections(blob, header=None):
     vsz = 4 if bits == RAW_BITS else 1
     pos = 16 + hl
     out = {}
-    if header.get("compact"):  # version 3: the packed stream where idx stood; the values only as fp32
+    if header.get("dense_packed"):  # version 4: the bit-packed dense stream, nothing else
+        names = [("mn", 4 * T), ("scale", 4 * T), ("packed", 4 * dense_packed_words(_seg_sizes(header), bits))]
+    elif header.get("compact"):  # version 3: the packed stream where idx stood; the values only as fp32
         names = [("mn", 4 * T), ("scale", 4 * T), ("packed", 4 * packed_words(K, bits))]
         if bits == RAW_BITS:
             names.append(("vals", 4 * K))
@@ -223,7 +342,7 @@ def unpack(blob):
     if bytes(mv[:8]) != MAGIC:
         raise ValueError("not a COALAQ1 blob (bad magic)")
     ver, hl = struct.unpack_from("<II", mv, 8)
-    if ver not in (VERSION, VERSION_2, VERSION_3):
+    if ver not in (VERSION, VERSION_2, VERSION_3, VERSION_4):
         raise ValueError(f"unsupported COALAQ1 version {ver}")
     header = _parse_header(mv, hl)
     compact = ver == VERSION_3
@@ -231,20 +350,30 @@ def unpack(blob):
         raise ValueError("COALAQ1: version and header compact disagree")
     if (ver in (VERSION_2, VERSION_3)) != ("n_units" in header):
         raise ValueError("COALAQ1: version and header n_units disagree")
+    dense_packed = ver == VERSION_4
+    if dense_packed != bool(header.get("dense_packed")):
+        raise ValueError("COALAQ1: version and header dense_packed disagree")
     T, K = int(header["n_segments"]), int(header["total_k"])
     bits = int(header["bits"])
     vdt = np.dtype("<f4") if bits == RAW_BITS else np.dtype("u1")
     pos = 16 + hl
     out = []
     dense = bool(header.get("dense"))
-    if compact:
+    if dense_packed:
+        if not dense or not 1 <= bits <= 7 or K < 0:
+            raise ValueError("COALAQ1: bad dense_packed header (needs \"dense\" and bits 1..7)")
+        ns = _seg_sizes(header)
+        if sum(ns) != K:
+            raise ValueError("COALAQ1: dense header with k != n")
+        layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<u4"), dense_packed_words(ns, bits))]
+    elif compact:
         if dense or bits not in VALID_BITS or K < 0:
             raise ValueError("COALAQ1: bad compact header")
         layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<u4"), packed_words(K, bits)),
                   (vdt, K if bits == RAW_BITS else 0)]
     else:
         layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<i4"), 0 if dense else K), (vdt, K)]
-    if ver != VERSION:
+    if ver in (VERSION_2, VERSION_3):
         layout.append((np.dtype("<i4"), int(header["n_units"])))
     for dt, n in layout:
         pos += _pad16(pos)
@@ -256,6 +385,8 @@ def unpack(blob):
     raw = bytes(mv[pos:])
     if dense and K != sum(int(e["n"]) for e in header["entries"] if e["kind"] == "seg"):
         raise ValueError("COALAQ1: dense header with k != n")
+    if dense_packed:  # the uint8 codes, rebuilt: what a version-1 dense blob carries
+        return (header, out[0], out[1], np.zeros(0, dtype="<i4"), unpack_dense_codes(out[2], ns, bits), raw, None)
     ustart = out[4] if ver != VERSION else None
     if compact:
         ns = [int(e["n"]) for e in header["entries"] if e["kind"] == "seg"]

@@ -3221,6 +3221,173 @@ __global__ __launch_bounds__(BLOCK) void k_unpack(Params P, const uint32_t* __re
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// bit-packed dense codes (wire v4): a dense plan's uint8 codes as B-bit fields, B = bits (1..8)
+//   segment s (plan row order) owns W_s = ceil(n_s B / 32) words at word offset pw_s = sum of W_t, t < s; entry e of
+//   the segment (its code at vals[out_off_s + e]) occupies bits [e B, (e + 1) B) of that sub-stream, little-endian
+//   (bit t is bit t % 32 of word t / 32), the last word's padding bits zero.
+// A segment's sub-stream starts on a word, so does every 4096-element unit of it: unit u_s at word pw_s + 128 B u_s.
+// One wave per unit owns whole words: plain stores, no atomics.
+//   k_pack_dense     a lane takes 32-entry groups (two per unit): 32 codes -> B words
+//   k_unpack_dense   the inverse: B words -> 32 codes, written inside vals[out_off_s + [0, n_s)) only
+//   k_dense_deq_packed  k_dense_deq reading the stream itself: a lane's four elements of a row are 4 B bits
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t DPACK_E = 32;                      // entries per group: B whole words
+constexpr uint32_t DPACK_G = UNIT / DPACK_E / 64;     // groups per lane per unit (2)
+
+// the unit's words inside the stream and how many it owns (the segment's last unit: up to the segment's last word)
+template <uint32_t B>
+DEV const uint32_t* dense_unit_words(const uint32_t* packed, const uint64_t* pw, const UnitDev& U, uint32_t& nwords) {
+  nwords = ((uint32_t)U.len * B + 31u) >> 5;
+  return packed + pw[U.seg] + (uint64_t)(UNIT / 32u * B) * (U.start >> UNIT_SHIFT);
+}
+
+template <uint32_t B>
+__global__ __launch_bounds__(BLOCK) void k_pack_dense(Params P, const uint64_t* __restrict__ pw,
+                                                      const uint8_t* __restrict__ vals, uint32_t* __restrict__ packed) {
+  const uint32_t u = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id();
+  const uint64_t o = U.out_off + U.start;  // the unit's first code (k == n: entry e is element e)
+  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;  // (as k_dense_quant: whole dwords, start to end)
+  // range-checked to the unit's codes: a group's tail past len reads 0, which is the padding
+  const __amdgpu_buffer_rsrc_t rin =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(vals + o), (short)0, (int)U.len, 0x00020000);
+  uint32_t nwords;
+  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
+  const __amdgpu_buffer_rsrc_t rout =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+  uint32_t q[DPACK_G][DPACK_E / 4];  // four codes per dword
+#pragma unroll
+  for (uint32_t g = 0; g < DPACK_G; ++g) {
+    const uint32_t b0 = (g * 64 + lane) * DPACK_E;
+    if (vec) {  // (dword loads: the codes' start is 4-byte aligned, no more)
+#pragma unroll
+      for (uint32_t i = 0; i < DPACK_E / 4; ++i) q[g][i] = __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(b0 + 4 * i), 0, 0);
+    } else {
+#pragma unroll
+      for (uint32_t i = 0; i < DPACK_E / 4; ++i)
+        q[g][i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i), 0, 0) |
+                  ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i + 1), 0, 0) << 8) |
+                  ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i + 2), 0, 0) << 16) |
+                  ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i + 3), 0, 0) << 24);
+    }
+  }
+#pragma unroll
+  for (uint32_t g = 0; g < DPACK_G; ++g) {
+    uint32_t word[B];
+    uint64_t acc = 0;
+    uint32_t nb = 0, wi = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < DPACK_E; ++i) {  // (fully unrolled: nb and wi are compile-time values)
+      const uint32_t c = (q[g][i >> 2] >> ((i & 3u) * 8u)) & ((1u << B) - 1u);
+      acc |= (uint64_t)c << nb;
+      nb += B;
+      if (nb >= 32u) {
+        word[wi++] = (uint32_t)acc;
+        acc >>= 32;
+        nb -= 32u;
+      }
+    }
+    const uint32_t w0 = (g * 64 + lane) * B;  // words past the unit's own are dropped by the range check
+#pragma unroll
+    for (uint32_t i = 0; i < B; ++i) __builtin_amdgcn_raw_buffer_store_b32(word[i], rout, (int)((w0 + i) * 4u), 0, 0);
+  }
+}
+
+template <uint32_t B>
+__global__ __launch_bounds__(BLOCK) void k_unpack_dense(Params P, const uint64_t* __restrict__ pw,
+                                                        const uint32_t* __restrict__ packed, uint8_t* __restrict__ vals) {
+  const uint32_t u = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id();
+  const uint64_t o = U.out_off + U.start;
+  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;
+  uint32_t nwords;
+  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
+  const __amdgpu_buffer_rsrc_t rin =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+  // range-checked to the unit's codes: a store past len is dropped (only vals[out_off + [0, n)) is written)
+  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(vals + o, (short)0, (int)U.len, 0x00020000);
+  uint32_t w[DPACK_G][B + 1];
+#pragma unroll
+  for (uint32_t g = 0; g < DPACK_G; ++g) {
+    const uint32_t w0 = (g * 64 + lane) * B;
+#pragma unroll
+    for (uint32_t i = 0; i < B; ++i) w[g][i] = __builtin_amdgcn_raw_buffer_load_b32(rin, (int)((w0 + i) * 4u), 0, 0);
+    w[g][B] = 0u;
+  }
+#pragma unroll
+  for (uint32_t g = 0; g < DPACK_G; ++g) {
+    const uint32_t b0 = (g * 64 + lane) * DPACK_E;
+#pragma unroll
+    for (uint32_t d = 0; d < DPACK_E / 4; ++d) {
+      uint32_t c[4];
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {  // (compile-time word and shift of entry 4 d + j)
+        const uint32_t bit = (4 * d + j) * B, wd = bit >> 5, sh = bit & 31u;
+        uint32_t v = w[g][wd] >> sh;
+        if (sh + B > 32u) v |= w[g][wd + 1] << (32u - sh);
+        c[j] = v & ((1u << B) - 1u);
+      }
+      if (vec) {
+        __builtin_amdgcn_raw_buffer_store_b32(c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), rout, (int)(b0 + 4 * d), 0, 0);
+      } else {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)c[j], rout, (int)(b0 + 4 * d + j), 0, 0);
+      }
+    }
+  }
+}
+
+// k_dense_deq with its values read from the dense stream: lane l's four elements of row it are the 4 B bits at bit
+// (it * 64 + l) * 4 B of the unit's words — one word, or two when the field straddles (never for B = 1, 2, 4, 8). The
+// loads are range-checked to the unit's own words, which lie inside its segment's W_s: a field at the end reads 0
+// past them, never another segment's word or past the stream. Same dequantize, base + x and stores as k_dense_deq.
+template <uint32_t B, bool HASBASE, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_deq_packed(Params P, const uint64_t* __restrict__ pw,
+                                                            const uint32_t* __restrict__ packed) {
+  constexpr bool STRADDLE = (32u % (4u * B)) != 0u;
+  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id();
+  const float mn = P.cmn[U.seg], scale = P.cscale[U.seg];
+  uint32_t nwords;
+  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
+  const __amdgpu_buffer_rsrc_t rin =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+  uint32_t lo[UNIT_IT], hi[UNIT_IT];
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    const uint32_t wd = ((it * 64 + lane) * 4u * B) >> 5;
+    lo[it] = __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(wd * 4u), 0, 0);
+    hi[it] = STRADDLE ? __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(wd * 4u + 4u), 0, 0) : 0u;
+  }
+  const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
+  const __amdgpu_buffer_rsrc_t rb = unit_rsrc(HASBASE ? P.base + U.off : P.out + U.off, U.len);
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    const uint32_t sh = ((it * 64 + lane) * 4u * B) & 31u;
+    const uint32_t f = (uint32_t)((((uint64_t)hi[it] << 32) | lo[it]) >> sh);
+    constexpr uint32_t M = (1u << B) - 1u;
+    float4 x = make_float4(dequantize((uint8_t)(f & M), mn, scale), dequantize((uint8_t)((f >> B) & M), mn, scale),
+                           dequantize((uint8_t)((f >> (2 * B)) & M), mn, scale),
+                           dequantize((uint8_t)((f >> (3 * B)) & M), mn, scale));
+    if (HASBASE) {
+      const float4 b = unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16);
+      x = make_float4(b.x + x.x, b.y + x.y, b.z + x.z, b.w + x.w);
+    }
+    if ((U.len & 3u) == 0)
+      unit_store_x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
+    else
+      unit_store_x1x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
+  }
+}
+
 // k_gather: n scalars of `bytes` each, from their own storage (one device pointer each), into one contiguous
 // buffer — an update's passthrough entries (BatchNorm's int64 num_batches_tracked, one per layer) snapshotted
 // in one launch instead of a stack of tensor copies
@@ -3386,6 +3553,10 @@ struct coalac_plan {
   bool fork_sized = false;      // small segments beside >= FORK_MIN_LUNITS large units: the encode forks them to a
                                 // side stream unless the call says COALAC_FLAG_NO_FORK
   uint64_t span = 0, total_k = 0, ws_bytes = 0;
+  // dense plans: the bit-packed code stream (wire v4) — its length in words at the plan's code width, and each segment
+  // row's word offset in it (a device array inside meta)
+  uint64_t dense_words = 0;
+  const uint64_t* dense_pw = nullptr;
   Params proto{};  // what every call's Params starts as: the metadata pointers (into meta), counts, levels and ccap
   void* meta = nullptr;
   std::vector<SegDev> hsegs;  // host copy (aggregate validates the client-copy structure)
@@ -3626,6 +3797,28 @@ void launch_pack(uint32_t b, dim3 g, hipStream_t st, const int32_t* idx, const u
     launch_pack<B + 1>(b, g, st, idx, vals, out, K);
 }
 
+// the dense stream's entry points: their shared checks (*done: nothing to launch), and the code width -> kernel
+int dense_packed_args(coalac_plan_t plan, const char* who, bool null_arg, uint64_t packed_bytes, bool* done) {
+  *done = false;
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if (null_arg) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse plan's payload is coalac_pack's", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
+  if (packed_bytes < 4 * plan->dense_words)
+    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
+                (unsigned long long)(4 * plan->dense_words));
+  *done = plan->proto.n_units == 0;
+  return *done ? COALAC_OK : check_device(plan);
+}
+
+template <uint32_t B = 1, typename F>
+void with_code_bits(uint32_t b, F&& f) {
+  if (b == B)
+    f(std::integral_constant<uint32_t, B>{});
+  else if constexpr (B < 8)
+    with_code_bits<B + 1>(b, f);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3742,8 +3935,19 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
   p->small_1k = small_max <= SMALL_MAX_LATENCY;
   p->fork_sized = M.n_small && M.n_lunits >= FORK_MIN_LUNITS;
   p->ws_bytes = carve_workspace(M, p->dense, nullptr);
+  // a dense plan's bit-packed code stream (wire v4): each segment row's word offset, behind the tables in the plan's
+  // one allocation (the stream's kernels take the array as an argument of their own: it is not in Params)
+  std::vector<uint64_t> dense_pw;
+  if (p->dense && bits != 32) {
+    dense_pw.reserve(T.segs.size());
+    for (const SegDev& d : T.segs) {
+      dense_pw.push_back(p->dense_words);
+      p->dense_words += ((uint64_t)d.n * (uint64_t)bits + 31u) / 32u;
+    }
+  }
 
-  const size_t bytes = place_tables(T, M, nullptr, nullptr);
+  const size_t tables = place_tables(T, M, nullptr, nullptr);
+  const size_t bytes = tables + align_up(sizeof(uint64_t) * dense_pw.size(), 256);
   std::vector<uint8_t> host(bytes, 0);
   hipError_t e = hipMalloc(&p->meta, bytes);
   if (e != hipSuccess) {
@@ -3751,6 +3955,10 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
     return fail(COALAC_ENOMEM, "hipMalloc(%zu) for plan metadata failed: %s", bytes, hipGetErrorString(e));
   }
   place_tables(T, M, host.data(), static_cast<const uint8_t*>(p->meta));
+  if (!dense_pw.empty()) {
+    memcpy(host.data() + tables, dense_pw.data(), sizeof(uint64_t) * dense_pw.size());
+    p->dense_pw = reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(p->meta) + tables);
+  }
   e = hipMemcpy(p->meta, host.data(), bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     (void)hipFree(p->meta);
@@ -3948,6 +4156,66 @@ int coalac_unpack(coalac_plan_t plan, const void* d_packed, uint64_t packed_byte
                            packed_field_bits(plan));
       },
       plan->bits == 32);
+  return launched();
+}
+
+int coalac_plan_dense_packed_bytes(coalac_plan_t plan, uint64_t* bytes) {
+  if (!plan || !bytes) return fail(COALAC_EINVAL, "coalac_plan_dense_packed_bytes: plan or output pointer is NULL");
+  if (!plan->dense || plan->bits == 32)
+    return fail(COALAC_EINVAL, "coalac_plan_dense_packed_bytes: needs a dense plan (every k == n) with bits 1..8");
+  *bytes = 4 * plan->dense_words;
+  return COALAC_OK;
+}
+
+int coalac_pack_dense(coalac_plan_t plan, const void* d_vals, void* d_packed, uint64_t packed_bytes, void* stream) {
+  bool done = false;
+  int rc = dense_packed_args(plan, "coalac_pack_dense", !d_vals || !d_packed, packed_bytes, &done);
+  if (rc || done) return rc;
+  if (addr_bits(d_packed, d_vals) & 3) return fail(COALAC_EINVAL, "coalac_pack_dense: vals / packed must be 4-byte aligned");
+  const Params P = plan->proto;
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  with_code_bits((uint32_t)plan->bits, [&](auto b) {
+    hipLaunchKernelGGL((k_pack_dense<b.value>), g, dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P, plan->dense_pw,
+                       static_cast<const uint8_t*>(d_vals), static_cast<uint32_t*>(d_packed));
+  });
+  return launched();
+}
+
+int coalac_unpack_dense(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, void* d_vals, void* stream) {
+  bool done = false;
+  int rc = dense_packed_args(plan, "coalac_unpack_dense", !d_packed || !d_vals, packed_bytes, &done);
+  if (rc || done) return rc;
+  if (addr_bits(d_packed, d_vals) & 3) return fail(COALAC_EINVAL, "coalac_unpack_dense: packed / vals must be 4-byte aligned");
+  const Params P = plan->proto;
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  with_code_bits((uint32_t)plan->bits, [&](auto b) {
+    hipLaunchKernelGGL((k_unpack_dense<b.value>), g, dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P, plan->dense_pw,
+                       static_cast<const uint32_t*>(d_packed), static_cast<uint8_t*>(d_vals));
+  });
+  return launched();
+}
+
+int coalac_decode_packed(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_mn,
+                         const float* d_scale, const float* d_base, float* d_out, void* stream) {
+  bool done = false;
+  int rc = dense_packed_args(plan, "coalac_decode_packed", !d_packed || !d_mn || !d_scale || !d_out, packed_bytes, &done);
+  if (rc || done) return rc;
+  if (addr_bits(d_packed) & 3) return fail(COALAC_EINVAL, "coalac_decode_packed: packed must be 4-byte aligned");
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_decode_packed: output/base must be 16-byte aligned");
+  Params P = plan->proto;
+  set_payload(P, nullptr, nullptr, d_mn, d_scale);
+  P.base = d_base;
+  P.out = d_out;
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  const uint32_t* packed = static_cast<const uint32_t*>(d_packed);
+  with_code_bits((uint32_t)plan->bits, [&](auto b) {
+    with_flags(
+        [&](auto h, auto x) {
+          hipLaunchKernelGGL((k_dense_deq_packed<b.value, h.value, x.value>), g, dim3(BLOCK), 0,
+                             static_cast<hipStream_t>(stream), P, plan->dense_pw, packed);
+        },
+        d_base != nullptr, !plan->decode_latency);
+  });
   return launched();
 }
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define COALAC_ABI_VERSION 7
+#define COALAC_ABI_VERSION 8
 
 enum {
   COALAC_OK = 0,
@@ -61,7 +61,9 @@ enum {
  * coalac_ef_accumulate / coalac_ef_commit — a client-side residual memory around an unchanged encode; no existing
  * entry point changes. ABI 7 adds the compact payload's coalac_plan_packed_bytes / coalac_pack / coalac_unpack — a
  * lossless repacking of idx / vals after an unchanged encode and before an unchanged decode; again no existing entry
- * point, plan query or workspace size changes.) */
+ * point, plan query or workspace size changes. ABI 8 adds the bit-packed dense codes' coalac_plan_dense_packed_bytes /
+ * coalac_pack_dense / coalac_unpack_dense / coalac_decode_packed — the same kind of lossless repacking for a dense
+ * plan's uint8 codes (wire v4); once more nothing that existed changes.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -175,6 +177,30 @@ int coalac_pack(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, vo
                 void* stream);
 int coalac_unpack(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const uint32_t* d_ustart,
                   int32_t* d_idx, void* d_vals, void* stream);
+
+/* Bit-packed dense codes (wire v4): the uint8 codes of a DENSE plan (every k == n) with code width b = bits, 1 <= b <= 8
+ * (the host packs only b <= 7: at 8 the stream is as long as the codes), as b-bit fields:
+ *
+ *   segment s, in the plan's row order, owns W_s = ceil(n_s b / 32) uint32 words at word offset pw_s = sum of W_t, t < s
+ *   (an empty segment owns none; pw_s does not depend on out_off); the stream is P = sum of W_s words;
+ *   entry e of segment s — its code vals[out_off_s + e] — occupies bits [e b, (e + 1) b) of the segment's sub-stream,
+ *   little-endian as above (bit t is bit t % 32 of word t / 32); the padding bits of a segment's last word are zero.
+ *
+ * Every 4096-element unit of a segment therefore starts on a word (unit u_s at word pw_s + 128 b u_s), and one wave per
+ * unit owns whole words. coalac_pack_dense writes only the words [pw_s, pw_s + W_s) of the plan's segments;
+ * coalac_unpack_dense, its inverse, only vals[out_off_s + [0, n_s)) — the adapter for every consumer of uint8 codes
+ * (coalac_decode, coalac_aggregate, coalac_ef_commit). coalac_decode_packed is coalac_decode of a dense plan reading the
+ * stream itself, with no byte-per-element intermediate: d_out (and d_base, fused: d_out = d_base + decoded) as
+ * coalac_decode takes them, the result bit-identical to coalac_unpack_dense followed by coalac_decode. Any b-bit field
+ * is a legal code, so an untrusted stream can mis-decode but not produce a code above 2^b - 1; padding bits are ignored.
+ * Each call is one asynchronous launch on `stream`: no allocation, no workspace, no host synchronisation. Any NULL
+ * pointer (d_base excepted), a sparse plan, a plan with bits == 32, or a packed_bytes below
+ * coalac_plan_dense_packed_bytes (= 4 P) is COALAC_EINVAL; d_packed and d_vals are 4-byte aligned. */
+int coalac_plan_dense_packed_bytes(coalac_plan_t plan, uint64_t* bytes);
+int coalac_pack_dense(coalac_plan_t plan, const void* d_vals, void* d_packed, uint64_t packed_bytes, void* stream);
+int coalac_unpack_dense(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, void* d_vals, void* stream);
+int coalac_decode_packed(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_mn,
+                         const float* d_scale, const float* d_base, float* d_out, void* stream);
 
 /* Profiling variants: identical work, plus hipEventRecord(events[i], stream) between kernels.
  * encode: [0] before k_sample, [1] after k_sample, [2] after k_scan, [3] after the select kernels
