@@ -56,6 +56,10 @@ SIGNATURES = [
     ("coalac_pack_dense", _I, [_P, _P, _P, _U64, _P]),
     ("coalac_unpack_dense", _I, [_P, _P, _U64, _P, _P]),
     ("coalac_decode_packed", _I, [_P, _P, _U64, _P, _P, _P, _P, _P]),
+    # block-wise dense: plan, in, seg pointers, base, bmn, bscale, packed, packed_bytes, stream / plan, packed,
+    # packed_bytes, bmn, bscale, base, out, stream
+    ("coalac_encode_block", _I, [_P, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    ("coalac_decode_block", _I, [_P, _P, _U64, _P, _P, _P, _P, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -67,7 +71,7 @@ SIGNATURES = [
     ("coalac_debug_brackets", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _I]),
 ]
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class CodecError(RuntimeError):

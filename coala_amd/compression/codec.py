@@ -29,7 +29,7 @@ from . import _lib, wire
 from ._cache import IdentityCache
 from .clone import _recipe, _reuse_after, _segment_views, module_with_state, release_decode_pool
 from .plan import CodecPlan, Encoded
-from .spec import RAW_BITS, VALID_BITS
+from .spec import RAW_BITS, UNIT, VALID_BITS
 from .state import (FlatState, RawState, as_numpy, describe_state, describe_tensors,  # noqa: F401 (re-exported)
                     flatten_state, layout_of, module_tensors)
 from .state import (_check_same_layout, _data_ptr, _decode_layout, _dense_elements, _describe, _get_device,
@@ -99,7 +99,9 @@ class CompressedUpdate:
 
     Holds the encoded buffers (device tensors right after encode; CPU tensors after unpickling) and the
     raw passthrough entries. Pickles to the COALAQ1 blob (wire.py). A compact carrier (header "compact": wire
-    v3) also holds the packed entry stream, `packed`, and ships that instead of idx and the uint8 codes.
+    v3) also holds the packed entry stream, `packed`, and ships that instead of idx and the uint8 codes. A block-wise
+    carrier (header "blockwise": wire v5) holds one mn / scale per 4096-element block and the bit-packed code stream;
+    its uint8 codes exist only where a blob was unpacked on the host.
     """
 
     def __init__(self, header, encoded, raw, blob=None, packed=None):
@@ -123,7 +125,7 @@ class CompressedUpdate:
         """A compact carrier's packed entry stream (wire.py, version 3), or a dense-packed carrier's bit-packed code
         stream (version 4), as a uint32 tensor; else None. Packed on the GPU right after the encode where the plan can
         (CodecPlan.pack / pack_dense); otherwise on the host, on first use (a received carrier: its blob's section)."""
-        if self.header.get("dense_packed"):
+        if self.header.get("dense_packed") or self.header.get("blockwise"):
             if self._packed[0] is None:
                 blob = self._blob[0]
                 if blob is not None:
@@ -150,6 +152,8 @@ class CompressedUpdate:
         vb = 4 if h["bits"] == RAW_BITS else 1
         ib = 0 if h["ratio"] >= 1.0 else 4  # ratio 1: indices implied, not shipped (wire.py "dense")
         raw_b = _raw_nbytes(self.raw)
+        if h.get("blockwise"):  # mn, scale per block and the bit-packed code stream
+            return 8 * h["n_blocks"] + 4 * wire.dense_packed_words(self._seg_sizes(), h["bits"]) + raw_b
         if h.get("dense_packed"):  # mn, scale and the bit-packed code stream
             return 8 * h["n_segments"] + 4 * wire.dense_packed_words(self._seg_sizes(), h["bits"]) + raw_b
         if h.get("compact"):  # the packed stream, and the values only as fp32
@@ -187,9 +191,14 @@ class CompressedUpdate:
         # the header (with each raw entry's blob offset) depends on the layout and the raw byte counts only
         hjson = _PACKED_HEADERS.get(h["entries"], (h["ratio"], h["bits"], h["mode"], h["n_segments"], h.get("total_k"),
                                                    h.get("n_units"), tuple(map(len, rawb.values())),
-                                                   bool(h.get("compact")), bool(h.get("dense_packed"))), header_json)
+                                                   bool(h.get("compact")), bool(h.get("dense_packed")),
+                                                   h.get("blockwise"), h.get("n_blocks")), header_json)
         enc = self.encoded
         rawbytes = b"".join(rawb[e["name"]] for e in h["entries"] if e["kind"] == "raw")
+        if h.get("blockwise"):  # wire v5: the per-block ranges and the stream — nothing else is copied
+            arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device))
+            return wire.pack({"dense": True, "blockwise": h["blockwise"], "n_blocks": h["n_blocks"]}, arrs[0], arrs[1],
+                             None, None, rawbytes, header_json=hjson, packed=arrs[2])
         if h.get("dense_packed"):  # wire v4: the bit-packed stream instead of the uint8 codes, which are not copied
             arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device))
             return wire.pack({"dense": True, "dense_packed": True}, arrs[0], arrs[1], None, None, rawbytes,
@@ -214,10 +223,13 @@ class CompressedUpdate:
         blob's region (mn ... ustart) holds the packed stream: idx / vals are then materialised on the device by
         `plan`.unpack (the decoding plan of this update; without one, the host-unpacked buffers are copied). A
         dense-packed blob (wire v4) for a plan that decodes the stream (decode_packed): its mn ... packed region, the
-        stream staying packed on the device (_dense_packed_to)."""
+        stream staying packed on the device (_dense_packed_to); a block-wise blob (wire v5) likewise, always: its
+        decode (decode_block) reads nothing but the stream."""
         device = torch.device(device)
         blob = self._blob[0]
         compact = bool(self.header.get("compact"))
+        if self.header.get("blockwise"):
+            return self._dense_packed_to(device, staging if device.type == "cuda" else None)
         if self.header.get("dense_packed") and device.type == "cuda" and getattr(plan, "decode_packed", None) is not None:
             return self._dense_packed_to(device, staging)
         if (staging is None or device.type != "cuda" or blob is None or self.header.get("dense")
@@ -249,7 +261,7 @@ class CompressedUpdate:
                        view("scale", torch.float32), view("ustart", torch.int32) if "ustart" in sec else None)
 
     def _dense_packed_to(self, device, staging):
-        """encoded_to of a dense-packed carrier for a plan that reads the stream: an Encoded whose `packed` is the
+        """encoded_to of a dense-packed (or block-wise) carrier for a plan that reads the stream: an Encoded whose `packed` is the
         bit-packed stream on `device`. A received carrier moves ONE pinned host-to-device copy of its blob's mn ...
         packed region and has no uint8 codes there (vals None: CodecPlan.unpack_dense makes them for who needs them);
         a carrier whose buffers are on the device already is handed out as it is."""
@@ -348,9 +360,15 @@ class UpdateCodec:
                §13): `bits` bits per element instead of a whole byte — the download direction's payload, or a
                pure-quantisation upload. Lossless and self-describing, as compact is. At bits 8 or 32, or below ratio
                1, the payload is what it is without the option. Off by default.
+        blockwise: ratio-1 (dense) updates with bits 1..8 are quantised block-wise (wire v5): one
+               min / scale pair per 4096-element block instead of one per tensor, so a single large weight no longer
+               sets the step of its whole tensor; the codes always travel bit-packed, and the encode is one pass over
+               the update. Applies where pack_dense applies (and wins over it when both are set); below ratio 1 or at
+               bits 32 it is ignored. Not combinable with error feedback (residual=). Off by default.
     """
 
-    def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True, compact=False, pack_dense=False):
+    def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True, compact=False, pack_dense=False,
+                 blockwise=False):
         if not (0.0 < float(ratio) <= 1.0):
             raise ValueError(f"ratio must be in (0, 1], got {ratio}")
         if bits not in VALID_BITS:
@@ -361,6 +379,7 @@ class UpdateCodec:
         self.recycle = bool(recycle)
         self.compact = bool(compact)
         self.pack_dense = bool(pack_dense)
+        self.blockwise = bool(blockwise)
         self.backend = backend if backend is not None else HipBackend()
         self._plans = {}
         self._plan_fast = IdentityCache(32)  # (sizes object; ratio, bits, clients, device) -> plan
@@ -454,6 +473,14 @@ class UpdateCodec:
         device = torch.device(device)
         base_flat = _delta_base(self.mode, entries, base, device, need_base)
         plan = self.plan_for(L.sizes_key, device)
+        blockwise = self.blockwise and self.ratio >= 1.0 and self.bits != RAW_BITS and _all_kept(plan)
+        if blockwise:
+            if residual is not None:
+                raise ValueError("block-wise quantisation cannot be combined with error feedback (residual=): the "
+                                 "commit reads per-segment codes")
+            if getattr(plan, "encode_block", None) is None:
+                raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
+                                   "has no encode_block: block-wise quantisation is not available on it")
         if residual is not None:
             if getattr(plan, "ef_accumulate", None) is None or getattr(plan, "ef_commit", None) is None:
                 raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
@@ -463,7 +490,7 @@ class UpdateCodec:
                 raise ValueError(f"residual: need float32[{int(plan.table.span)}] on {device} (new_residual), got "
                                  f"{residual.dtype}{list(residual.shape)} on {residual.device}")
         cur = torch.cuda.current_stream(device) if device.type == "cuda" else None  # (looked up once per call)
-        ws = self._workspace(plan, cur)
+        ws = None if blockwise else self._workspace(plan, cur)
         dev_index = device.index if device.type == "cuda" else -1  # (Tensor.get_device(): -1 on the CPU)
         in_place = getattr(plan, "encode_segments", None) is not None
         if in_place:  # every segment on the plan's device, contiguous, 16-B aligned (one pass per property)
@@ -481,6 +508,16 @@ class UpdateCodec:
                             and not any(p & 15 for p in ptrs))
                 if in_place:
                     self._checked_ptrs[id(plan)] = ptrs
+        if blockwise:
+            # wire v5: one pass — ranges per block, the bit-packed stream written directly (no workspace, no codes)
+            if in_place:
+                bmn, bscale, packed = plan.encode_block(tensors=segs, base=base_flat, stream=cur, checked=True, ptrs=ptrs)
+            else:
+                bmn, bscale, packed = plan.encode_block(flat=flatten_state(state_fn(), device=device).flat,
+                                                        base=base_flat, stream=cur)
+            header.update(total_k=int(plan.table.total_k), blockwise=UNIT, n_blocks=int(plan.table.n_units))
+            enc = Encoded(torch.empty(0, dtype=torch.int32, device=bmn.device), None, bmn, bscale, None, packed)
+            return CompressedUpdate(header, enc, raw() if callable(raw) else raw, packed=packed)
         if residual is not None:
             # error feedback, in stream order: residual = (state - base) + residual; the plain encode of that; then
             # residual -= what the payload reconstructs, at its kept entries
@@ -626,7 +663,9 @@ class UpdateCodec:
                 with torch.cuda.stream(side):
                     enc = update.encoded_to(device, staging=self._staging, plan=plan)
                     self._staged(side)
-                    if enc.packed is not None:  # a dense-packed update: decoded from the bit stream itself
+                    if h.get("blockwise"):  # per-block ranges: its own decode, from the bit stream
+                        flat = plan.decode_block(enc.packed, enc.mn, enc.scale, base=base_flat, out=out, stream=side)
+                    elif enc.packed is not None:  # a dense-packed update: decoded from the bit stream itself
                         flat = plan.decode_packed(enc.packed, enc.mn, enc.scale, base=base_flat, out=out, stream=side)
                     else:
                         flat = plan.decode(enc, base=base_flat, out=out, stream=side)
@@ -636,8 +675,13 @@ class UpdateCodec:
             else:
                 if into is not None:
                     _reuse_after(into, None, None)
-                enc = update.encoded.to(device, non_blocking=True)
-                flat = plan.decode(enc, base=base_flat, out=None if into is None else into.flat)
+                if h.get("blockwise"):
+                    enc = update.encoded_to(device)
+                    flat = plan.decode_block(enc.packed, enc.mn, enc.scale, base=base_flat,
+                                             out=None if into is None else into.flat)
+                else:
+                    enc = update.encoded.to(device, non_blocking=True)
+                    flat = plan.decode(enc, base=base_flat, out=None if into is None else into.flat)
                 if into is not None:
                     _copy_raw_groups(raw, into)
         elif into is not None:
@@ -710,10 +754,14 @@ class UpdateCodec:
         h0 = updates[0].header
         for u in updates[1:]:
             h = u.header
-            if (h["ratio"], h["bits"], h["mode"], h["entries"], bool(h.get("compact")), bool(h.get("dense_packed"))) != \
+            if (h["ratio"], h["bits"], h["mode"], h["entries"], bool(h.get("compact")), bool(h.get("dense_packed")),
+                    bool(h.get("blockwise"))) != \
                     (h0["ratio"], h0["bits"], h0["mode"], h0["entries"], bool(h0.get("compact")),
-                     bool(h0.get("dense_packed"))):
+                     bool(h0.get("dense_packed")), bool(h0.get("blockwise"))):
                 raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode / payload format")
+        if h0.get("blockwise"):
+            raise ValueError("fused aggregation reads per-segment codes: block-wise updates are decoded one by one "
+                             "(decode_module)")
         sizes = [e["n"] for e in h0["entries"] if e["kind"] == "seg"]
         device = self.backend.default_device() if device is None else torch.device(device)
         base_flat = _delta_base(h0["mode"], h0["entries"], base, device,

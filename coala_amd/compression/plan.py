@@ -22,7 +22,9 @@ class Encoded:
     index of its first kept entry — a decoder then needs no search of the idx lists (None: not available).
     packed: a dense-packed update's bit-packed code stream (wire v4, uint32[P]) where its holder has it on the
     buffers' device — CodecPlan.decode_packed reads it instead of vals, which may then be None until
-    CodecPlan.unpack_dense makes the codes (None: the update is not dense-packed, or only its codes are here)."""
+    CodecPlan.unpack_dense makes the codes (None: the update is not dense-packed, or only its codes are here). A
+    block-wise update (wire v5): mn / scale hold one entry per 4096-element block, packed is the stream
+    CodecPlan.decode_block reads, vals is None unless a blob was unpacked on the host."""
     idx: torch.Tensor
     vals: torch.Tensor
     mn: torch.Tensor
@@ -469,6 +471,68 @@ class CodecPlan:
             rc = self._lib.coalac_decode_packed(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(mn),
                                                 _ptr(scale), _ptr(base), _ptr(out), _stream_handle(stream))
         _lib.check(rc, "coalac_decode_packed")
+        return out
+
+    # -- block-wise dense quantisation (wire v5) --------------------------------------------------
+    def empty_block_encoded(self):
+        """(bmn fp32[n_units], bscale fp32[n_units], packed uint32[dense_packed_words]) as views of ONE allocation
+        (16-byte aligned each): the outputs of encode_block."""
+        U, P = self.n_units, self.dense_packed_words
+        a = (4 * U + 15) // 16 * 16
+        buf = torch.empty(2 * a + 4 * P, dtype=torch.uint8, device=self.device)
+        return (buf[:4 * U].view(torch.float32), buf[a:a + 4 * U].view(torch.float32),
+                buf[2 * a:2 * a + 4 * P].view(torch.uint32))
+
+    def _check_block_ranges(self, who, *ts):
+        for t in ts:
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or \
+                    t.numel() < self.n_units:
+                raise ValueError(f"{who}: need bmn / bscale as float32[{self.n_units}] on {self.device}, got "
+                                 f"{t.dtype}[{t.numel()}] on {t.device}")
+
+    def encode_block(self, flat=None, tensors=None, base=None, out=None, stream=None, checked=False, ptrs=None):
+        """Block-wise encode of a dense plan (coalac_encode_block): every 4096-element unit quantised over its own
+        range, in one pass -> (bmn fp32[n_units], bscale fp32[n_units], packed uint32[dense_packed_words]), the code
+        stream in wire v4's layout. The update is read from `flat` (fp32[span]) or from `tensors` (one per segment, as
+        encode_segments reads them) — exactly one of the two; base: flat fp32[span] (delta mode). out: such a triple
+        to write into. Asynchronous on `stream`."""
+        self._need_dense("encode_block")
+        if (flat is None) == (tensors is None):
+            raise ValueError("encode_block: give exactly one of flat and tensors")
+        self._check_flat(base, "base")
+        launch = torch.cuda.current_stream(self.device) if stream is None else stream
+        if tensors is not None:
+            seg, x = _ptr(self.segment_pointers(tensors, checked=checked, ptrs=ptrs, stream=launch)), _ptr(None)
+        else:
+            self._check_flat(flat, "input")
+            seg, x = _ptr(None), _ptr(flat)
+        if out is None:
+            with _on(stream):
+                out = self.empty_block_encoded()
+        bmn, bscale, packed = out
+        self._check_block_ranges("encode_block", bmn, bscale)
+        self._check_dense_packed(packed, "packed output")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_encode_block(self._h, x, seg, _ptr(base), _ptr(bmn), _ptr(bscale), _ptr(packed),
+                                               ctypes.c_uint64(4 * packed.numel()), ctypes.c_void_p(launch.cuda_stream))
+        _lib.check(rc, "coalac_encode_block")
+        return bmn, bscale, packed
+
+    def decode_block(self, packed, bmn, bscale, base=None, out=None, stream=None):
+        """Decode of a block-wise stream (coalac_decode_block: decode_packed with each unit's own range) -> dense flat
+        fp32[span] (+ base, fused). Asynchronous on `stream`."""
+        self._need_dense("decode_block")
+        self._check_dense_packed(packed, "packed stream")
+        self._check_block_ranges("decode_block", bmn, bscale)
+        self._check_flat(base, "base")
+        with _on(stream):
+            if out is None:
+                out = self.empty_flat() if base is None else torch.empty_like(base)
+        self._check_flat(out, "output")
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_decode_block(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(bmn),
+                                               _ptr(bscale), _ptr(base), _ptr(out), _stream_handle(stream))
+        _lib.check(rc, "coalac_decode_block")
         return out
 
     def unit_starts(self, idx, stream=None):

@@ -35,6 +35,10 @@ Behaviour:
   * bit-packed dense codes (opt-in, `codec_download_pack = True` on the server for the download, `codec_pack_dense =
     True` on a client for a ratio-1 upload; bits below 8): every code travels as `bits` bits instead of a byte (wire
     v4). Lossless and self-describing: the receiver has no switch.
+  * block-wise quantisation (opt-in, `codec_download_blockwise = True` on the server for the download, `codec_blockwise
+    = True` on a client for a ratio-1 upload; any bits <= 8): one min / scale pair per 4096-element block instead of
+    one per tensor, the codes bit-packed (wire v5). Self-describing; such uploads are decoded one by
+    one, not fused; not combinable with error feedback.
   * calculate_model_size(): reports the real payload size for a carrier (base.py:155, 474-487).
   * server decompression(model): CompressedUpdate -> a NEW nn.Module (never aliases self.model, which
     aggregation overwrites, base.py:571) built on the pre-aggregation global model (delta mode: w_global
@@ -104,12 +108,21 @@ class _CodecOwner:
     codec_backend = None
     codec_recycle = True  # decoded modules are reused once released (UpdateCodec recycle; False: never)
 
+    def _codec_blockwise(self):
+        """codec_blockwise, refused next to codec_error_feedback: the residual's commit reads per-segment codes."""
+        on = bool(getattr(self, "codec_blockwise", False))
+        if on and getattr(self, "codec_error_feedback", False):
+            raise ValueError("codec_blockwise cannot be combined with codec_error_feedback: the error-feedback commit "
+                             "reads per-segment codes, a block-wise payload has one range per 4096-element block")
+        return on
+
     def _codec(self):
         c = self.__dict__.get("_update_codec")
         if c is None:
             c = UpdateCodec(self.codec_ratio, self.codec_bits, self.codec_mode, self.codec_backend,
                             recycle=self.codec_recycle, compact=getattr(self, "codec_compact", False),
-                            pack_dense=getattr(self, "codec_pack_dense", False))
+                            pack_dense=getattr(self, "codec_pack_dense", False),
+                            blockwise=self._codec_blockwise())
             self.__dict__["_update_codec"] = c
         return c
 
@@ -135,6 +148,11 @@ class CompressionClientMixin(_CodecOwner):
     # element travels as codec_bits bits instead of a whole byte. Lossless and self-describing, as codec_compact is.
     # Off by default; below ratio 1, or at 8 or 32 bits, it changes nothing.
     codec_pack_dense = False
+
+    # block-wise quantisation for ratio-1 uploads (wire v5): one min / scale pair per 4096-element block
+    # instead of one per tensor, the codes always bit-packed. Applies where codec_pack_dense applies (bits 8 included)
+    # and wins over it; self-describing. Not combinable with codec_error_feedback (ValueError). Off by default.
+    codec_blockwise = False
 
     def reset_error_feedback(self):
         """Zero this client's residual (e.g. when it joins a new task with the same model)."""
@@ -252,12 +270,15 @@ class CompressionServerMixin(_CodecOwner):
     codec_download_bits = 8
     codec_download_pack = False   # bit-pack the download's codes (wire v4): codec_download_bits bits per element
                                   # instead of a byte, at ratio 1 and fewer than 8 bits; the receiver has no switch
+    codec_download_blockwise = False  # block-wise download (wire v5): one min / scale pair per 4096-element block
+                                      # instead of one per tensor, codes bit-packed; ratio 1, any bits <= 8; wins over
+                                      # codec_download_pack
 
     def _download_codec(self):
         c = self.__dict__.get("_download_update_codec")
         if c is None:
             c = UpdateCodec(self.codec_download_ratio, self.codec_download_bits, "weights", self.codec_backend,
-                            pack_dense=self.codec_download_pack)
+                            pack_dense=self.codec_download_pack, blockwise=self.codec_download_blockwise)
             self.__dict__["_download_update_codec"] = c
         return c
 
@@ -365,10 +386,13 @@ class CompressionServerMixin(_CodecOwner):
             if getattr(server_conf, "aggregation_strategy", None) == EQUAL_AVERAGE:
                 weights = [1 for _ in models]
             h0 = models[0].header
-            if all(m.header["entries"] == h0["entries"] and
+            # (a block-wise upload has one range per block, which the fused kernel cannot read: such a round — and one of
+            # mixed formats — is decoded upload by upload below)
+            if not h0.get("blockwise") and all(
+                   m.header["entries"] == h0["entries"] and
                    (m.header["ratio"], m.header["bits"], m.header["mode"], bool(m.header.get("compact")),
-                    bool(m.header.get("dense_packed"))) ==
-                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")), bool(h0.get("dense_packed")))
+                    bool(m.header.get("dense_packed")), bool(m.header.get("blockwise"))) ==
+                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")), bool(h0.get("dense_packed")), False)
                    for m in models):
                 base = self._global_snapshot() if h0["mode"] == "delta" else None
                 codec = self._codec()

@@ -7,8 +7,8 @@ self-describing because remote clients never receive new config keys (OperateCon
 
 Layout (little-endian):
     0   8B   magic b"COALAQ1\\0"
-    8   u32  format version (4 when the header has "dense_packed", 3 when it has "compact", 2 when it has "n_units"
-             only, else 1)
+    8   u32  format version (5 when the header has "blockwise", 4 when it has "dense_packed", 3 when it has "compact",
+             2 when it has "n_units" only, else 1)
     12  u32  header length H
     16  H    UTF-8 JSON header: ratio, bits, mode, n_segments, total_k, [n_units], entries[]
              entry = {"name", "dtype", "shape", "kind": "seg", "seg": i, "n", "k", "out_off"}
@@ -54,6 +54,18 @@ Version 4, BIT-PACKED DENSE CODES (opt-in, "dense" updates with bits 1..7 only; 
     k_pack_dense / k_unpack_dense / k_dense_deq_packed (coalac.hip) produce and read the same bytes. unpack() of a
     version-4 blob returns the rebuilt uint8 codes, so validate() and every consumer of codes sees what it sees for
     a version-1 / 2 dense blob.
+
+Version 5, BLOCK-WISE DENSE QUANTISATION (opt-in, "dense" updates with bits 1..8; header keys "dense": true,
+"blockwise": 4096 and "n_blocks": U):
+         mn f32[U] | scale f32[U] | packed u32[P] | raw bytes
+    One quantisation range per 4096-element block instead of one per segment. Block index = unit index: segment by
+    segment in header order, ceil(n_s / 4096) blocks each, U = their sum; block u, the u_s-th of segment s, covers the
+    segment's elements [4096 u_s, min(n_s, 4096 (u_s + 1))). CodecSpec v1 applies to the block as if it were a segment
+    of its own with k = n: mn_u / mx_u its NaN-ignoring min / max (+ 0.0f), scale_u = 0 if mx_u == mn_u else
+    (mx_u - mn_u) / L, the same quantise, decode mn_u + float(q) * scale_u. The code stream is version 4's, bit for bit
+    (also at bits 8, where it is simply the codes): the same W_s, pw_s, field order and zero padding, so a block starts
+    at word pw_s + 128*b*u_s. The blob is 8 U + 4 P + raw payload bytes (plus header and alignment). unpack() returns
+    mn / scale of length U and the rebuilt uint8 codes. block_count / block_table below are the block order on the host.
 """
 import json
 import struct
@@ -69,6 +81,7 @@ VERSION = 1     # mn | scale | idx | vals | raw
 VERSION_2 = 2   # ... | vals | ustart | raw
 VERSION_3 = 3   # mn | scale | packed | [vals f32] | ustart | raw  (header "compact": true)
 VERSION_4 = 4   # mn | scale | packed | raw  (header "dense": true, "dense_packed": true)
+VERSION_5 = 5   # mn[U] | scale[U] | packed | raw  (header "dense": true, "blockwise": 4096, "n_blocks": U)
 INDEX_BITS = 12  # low index bits in a packed field: log2(UNIT), the position inside the entry's 4096-element unit
 
 
@@ -228,24 +241,62 @@ def _seg_sizes(header):
     return [int(e["n"]) for e in header["entries"] if e["kind"] == "seg"]
 
 
+def block_count(sizes):
+    """Blocks U of dense segments of `sizes` elements: the sum of ceil(n / 4096) (an empty segment has none)."""
+    n = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    return int(((n + UNIT - 1) // UNIT).sum())
+
+
+def block_table(sizes):
+    """The block-wise format's view of dense segments laid out back to back: one row (offset, length) per block, in
+    block order — what a decoder applies mn[u] / scale[u] to. int64[U, 2]."""
+    rows, off = [], 0
+    for n in (int(x) for x in sizes):
+        rows += [(off + a, min(UNIT, n - a)) for a in range(0, n, UNIT)]
+        off += n
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+
+
+def _check_blockwise(header, layout=True):
+    """The header rules of a block-wise (version 5) payload; returns (segment sizes, U). layout=False: the format keys
+    only (pack() is handed a header that may hold nothing else; the full header travels as header_json)."""
+    if not header.get("dense"):
+        raise ValueError("COALAQ1: \"blockwise\" needs a \"dense\" payload")
+    if isinstance(header["blockwise"], bool) or int(header["blockwise"]) != UNIT:
+        raise ValueError(f"COALAQ1: block size {header['blockwise']!r} (only {UNIT} is defined)")
+    if header.get("dense_packed") or header.get("compact") or "n_units" in header:
+        raise ValueError("COALAQ1: \"blockwise\" excludes \"dense_packed\", \"compact\" and per-unit starts")
+    if "bits" in header and not 1 <= int(header["bits"]) <= 8:
+        raise ValueError(f"COALAQ1: block-wise codes are 1..8 bits wide, not {header['bits']}")
+    if not layout:
+        return None, int(header.get("n_blocks", -1))
+    if "bits" not in header:
+        raise ValueError("COALAQ1: header without bits")
+    ns = _seg_sizes(header)
+    if sum(ns) != int(header["total_k"]):
+        raise ValueError("COALAQ1: dense header with k != n")
+    if "n_blocks" not in header or int(header["n_blocks"]) != block_count(ns):
+        raise ValueError("COALAQ1: header n_blocks is not the layout's block count")
+    return ns, int(header["n_blocks"])
+
+
 def pack(header, mn, scale, idx, vals, raw, header_json=None, ustart=None, packed=None):
     """numpy arrays + raw bytes -> blob (bytes). A "dense" header drops idx (it is implied). header_json: the
     header's JSON encoding, if the caller has it already. ustart: the per-unit starts (version 2; the header
     must then carry "n_units" = len(ustart)). packed: the packed entry stream (version 3, which needs ustart and a
     header with "compact": true): it stands where idx stood, and vals is the fp32 values at bits 32, else None.
     A header with "dense" and "dense_packed" (version 4): packed is the bit-packed dense stream, the only section
-    after mn and scale (idx, vals and ustart are not written)."""
+    after mn and scale (idx, vals and ustart are not written). A header with "blockwise" (version 5): mn / scale hold
+    one entry per block ("n_blocks" of them) and packed is the same stream."""
+    if header.get("blockwise"):
+        _, U = _check_blockwise(header, layout=False)
+        if packed is None or ustart is not None or len(mn) != U or len(scale) != U:
+            raise ValueError("COALAQ1: a block-wise payload needs the packed stream and one mn / scale per block")
+        return _pack_stream(VERSION_5, header, header_json, mn, scale, packed, raw)
     if header.get("dense_packed"):
         if not header.get("dense") or packed is None or ustart is not None or "n_units" in header:
             raise ValueError("COALAQ1: a dense-packed payload needs \"dense\", the packed stream and no per-unit starts")
-        h = header_json if header_json is not None else encode_header(header)
-        parts, size = [MAGIC, struct.pack("<II", VERSION_4, len(h)), h], 16 + len(h)
-        for arr in (np.ascontiguousarray(mn, "<f4"), np.ascontiguousarray(scale, "<f4"), np.ascontiguousarray(packed, "<u4")):
-            b = arr.tobytes()
-            parts += [b"\0" * _pad16(size), b]
-            size += _pad16(size) + len(b)
-        parts += [b"\0" * _pad16(size), bytes(raw)]
-        return b"".join(parts)
+        return _pack_stream(VERSION_4, header, header_json, mn, scale, packed, raw)
     if header.get("dense"):
         idx = np.zeros(0, dtype=np.int32)
     if (ustart is not None) != ("n_units" in header) or (ustart is not None and len(ustart) != header["n_units"]):
@@ -274,6 +325,18 @@ def pack(header, mn, scale, idx, vals, raw, header_json=None, ustart=None, packe
     p = _pad16(size)
     parts.append(b"\0" * p)
     parts.append(bytes(raw))
+    return b"".join(parts)
+
+
+def _pack_stream(ver, header, header_json, mn, scale, packed, raw):
+    """mn | scale | packed | raw, each 16-byte aligned, behind the header: the layout versions 4 and 5 share."""
+    h = header_json if header_json is not None else encode_header(header)
+    parts, size = [MAGIC, struct.pack("<II", ver, len(h)), h], 16 + len(h)
+    for arr in (np.ascontiguousarray(mn, "<f4"), np.ascontiguousarray(scale, "<f4"), np.ascontiguousarray(packed, "<u4")):
+        b = arr.tobytes()
+        parts += [b"\0" * _pad16(size), b]
+        size += _pad16(size) + len(b)
+    parts += [b"\0" * _pad16(size), bytes(raw)]
     return b"".join(parts)
 
 
@@ -317,7 +380,10 @@ def sections(blob, header=None):
     vsz = 4 if bits == RAW_BITS else 1
     pos = 16 + hl
     out = {}
-    if header.get("dense_packed"):  # version 4: the bit-packed dense stream, nothing else
+    if header.get("blockwise"):  # version 5: per-block ranges, then version 4's stream
+        U = int(header["n_blocks"])
+        names = [("mn", 4 * U), ("scale", 4 * U), ("packed", 4 * dense_packed_words(_seg_sizes(header), bits))]
+    elif header.get("dense_packed"):  # version 4: the bit-packed dense stream, nothing else
         names = [("mn", 4 * T), ("scale", 4 * T), ("packed", 4 * dense_packed_words(_seg_sizes(header), bits))]
     elif header.get("compact"):  # version 3: the packed stream where idx stood; the values only as fp32
         names = [("mn", 4 * T), ("scale", 4 * T), ("packed", 4 * packed_words(K, bits))]
@@ -334,17 +400,37 @@ def sections(blob, header=None):
     return header, out
 
 
+def _unpack_blockwise(mv, pos, header):
+    """unpack() of a version-5 blob: mn / scale per block, the uint8 codes rebuilt from the stream."""
+    ns, U = _check_blockwise(header)
+    bits = int(header["bits"])
+    out = []
+    for dt, n in ((np.dtype("<f4"), U), (np.dtype("<f4"), U), (np.dtype("<u4"), dense_packed_words(ns, bits))):
+        pos += _pad16(pos)
+        if pos + n * dt.itemsize > len(mv):
+            raise ValueError("COALAQ1: truncated blob")
+        out.append(np.frombuffer(mv, dtype=dt, count=n, offset=pos))
+        pos += n * dt.itemsize
+    pos += _pad16(pos)
+    return (header, out[0], out[1], np.zeros(0, dtype="<i4"), unpack_dense_codes(out[2], ns, bits), bytes(mv[pos:]), None)
+
+
 def unpack(blob):
     """blob -> (header dict, mn, scale, idx, vals, raw bytes, ustart or None). Arrays are read-only views of
     blob; a "dense" blob's idx is empty (implied). A compact (version 3) blob's idx and uint8 vals are rebuilt
-    from its packed stream (unpack_entries, with every segment's k = k_for(n, ratio) as validate() expects)."""
+    from its packed stream (unpack_entries, with every segment's k = k_for(n, ratio) as validate() expects). A
+    block-wise (version 5) blob's mn / scale have one entry per block."""
     mv = memoryview(blob)
     if bytes(mv[:8]) != MAGIC:
         raise ValueError("not a COALAQ1 blob (bad magic)")
     ver, hl = struct.unpack_from("<II", mv, 8)
-    if ver not in (VERSION, VERSION_2, VERSION_3, VERSION_4):
+    if ver not in (VERSION, VERSION_2, VERSION_3, VERSION_4, VERSION_5):
         raise ValueError(f"unsupported COALAQ1 version {ver}")
     header = _parse_header(mv, hl)
+    if (ver == VERSION_5) != ("blockwise" in header):
+        raise ValueError("COALAQ1: version and header blockwise disagree")
+    if ver == VERSION_5:
+        return _unpack_blockwise(mv, 16 + hl, header)
     compact = ver == VERSION_3
     if compact != bool(header.get("compact")):
         raise ValueError("COALAQ1: version and header compact disagree")

@@ -2773,6 +2773,23 @@ DEV void dense_unit_load(const Params& P, const UnitDev& U, float4 (&v)[UNIT_IT]
   }
 }
 
+// The dense quantise of one value (k_dense_quant, k_dense_block_quant). RCP: (x - mn) / scale as q = RN(a * y),
+// y = RN(1 / scale), then q + RN(a - q * scale) * y by two FMAs — the correctly rounded quotient (Markstein) when
+// neither the residual nor the quotient leaves the normal range, which scale in [2^-90, 2^90] ensures wherever the code
+// is not 0 (t >= 0.5 needs a >= 2^-91); below that both round to code 0. The caller picks RCP for such a scale (a
+// wave-uniform branch) and the IEEE division of `quantize` otherwise (scale 0, NaN, inf or extreme).
+DEV bool dense_rcp_scale(float scale) { return scale >= 0x1p-90f && scale <= 0x1p90f; }
+template <bool RCP>
+DEV uint32_t dense_code(float x, float mn, float scale, float y, float levels) {
+  if (!RCP) return quantize(x, mn, scale, levels);
+  const float a = x - mn;
+  const float q = a * y;
+  const float t = __builtin_fmaf(__builtin_fmaf(-q, scale, a), y, q);
+  const float rt = rintf(t);
+  if (!(rt > 0.0f)) return 0u;
+  return (uint32_t)(uint8_t)(rt < levels ? rt : levels);
+}
+
 template <bool DELTA, bool XCD>
 __global__ __launch_bounds__(BLOCK) void k_dense_minmax(Params P) {
   const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
@@ -2898,22 +2915,12 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
   } else {
     uint8_t* dst = static_cast<uint8_t*>(P.vals) + o;
     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(dst, (short)0, (int)U.len, 0x00020000);
-    // RCP: (x - mn) / scale as q = RN(a * y), y = RN(1 / scale), then q + RN(a - q * scale) * y by two FMAs — the
-    // correctly rounded quotient (Markstein) when neither the residual nor the quotient leaves the normal range,
-    // which scale in [2^-90, 2^90] ensures wherever the code is not 0 (t >= 0.5 needs a >= 2^-91); below that both
-    // round to code 0. The IEEE division sequence it replaces cost 3.5 us of the download step (profiles/r06_ab_dense_segred.txt)
+    // dense_code's reciprocal form: the IEEE division sequence it replaces cost 3.5 us of the download step
+    // (profiles/r06_ab_dense_segred.txt)
     auto codes = [&](auto rcp_tag) {
       constexpr bool RCP = decltype(rcp_tag)::value;
       const float y = RCP ? 1.0f / scale : 0.0f;
-      auto qz = [&](float x) -> uint32_t {
-        if (!RCP) return quantize(x, mn, scale, P.levels);
-        const float a = x - mn;
-        const float q = a * y;
-        const float t = __builtin_fmaf(__builtin_fmaf(-q, scale, a), y, q);
-        const float rt = rintf(t);
-        if (!(rt > 0.0f)) return 0u;
-        return (uint32_t)(uint8_t)(rt < P.levels ? rt : P.levels);
-      };
+      auto qz = [&](float x) -> uint32_t { return dense_code<RCP>(x, mn, scale, y, P.levels); };
 #pragma unroll
       for (uint32_t it = 0; it < UNIT_IT; ++it) {
         const uint32_t q0 = qz(v[it].x), q1 = qz(v[it].y), q2 = qz(v[it].z), q3 = qz(v[it].w);
@@ -2928,7 +2935,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
         }
       }
     };
-    if (scale >= 0x1p-90f && scale <= 0x1p90f)  // (uniform per wave; scale 0, NaN, inf or extreme: the division)
+    if (dense_rcp_scale(scale))  // (uniform per wave; scale 0, NaN, inf or extreme: the division)
       codes(std::true_type{});
     else
       codes(std::false_type{});
@@ -3347,15 +3354,13 @@ __global__ __launch_bounds__(BLOCK) void k_unpack_dense(Params P, const uint64_t
 // (it * 64 + l) * 4 B of the unit's words — one word, or two when the field straddles (never for B = 1, 2, 4, 8). The
 // loads are range-checked to the unit's own words, which lie inside its segment's W_s: a field at the end reads 0
 // past them, never another segment's word or past the stream. Same dequantize, base + x and stores as k_dense_deq.
-template <uint32_t B, bool HASBASE, bool XCD>
-__global__ __launch_bounds__(BLOCK) void k_dense_deq_packed(Params P, const uint64_t* __restrict__ pw,
-                                                            const uint32_t* __restrict__ packed) {
+// (dense_deq_packed_unit: one unit of it, with the range (mn, scale) its caller read — the segment's here, the unit's
+// own in k_dense_block_deq)
+template <uint32_t B, bool HASBASE>
+DEV void dense_deq_packed_unit(const Params& P, const UnitDev& U, const uint64_t* __restrict__ pw,
+                               const uint32_t* __restrict__ packed, float mn, float scale) {
   constexpr bool STRADDLE = (32u % (4u * B)) != 0u;
-  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
-  if (u >= P.n_units) return;
-  const UnitDev U = P.units[u];
   const uint32_t lane = lane_id();
-  const float mn = P.cmn[U.seg], scale = P.cscale[U.seg];
   uint32_t nwords;
   const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
   const __amdgpu_buffer_rsrc_t rin =
@@ -3386,6 +3391,115 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq_packed(Params P, const uint
     else
       unit_store_x1x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
   }
+}
+
+template <uint32_t B, bool HASBASE, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_deq_packed(Params P, const uint64_t* __restrict__ pw,
+                                                            const uint32_t* __restrict__ packed) {
+  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  dense_deq_packed_unit<B, HASBASE>(P, U, pw, packed, P.cmn[U.seg], P.cscale[U.seg]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// block-wise dense quantisation (wire v5): every 4096-element unit of a dense plan is quantised over its
+// OWN range — CodecSpec v1 applied to the unit as if it were a segment with k = n — and the codes leave as wire v4's
+// B-bit stream, in one pass: no min / max pre-pass, no segment reduce, no byte-per-element intermediate.
+//   k_dense_block_quant  one wave per unit: load (16 float4 per lane), the wave's NaN-ignoring min / max -> bmn[u],
+//                        bscale[u], quantise (dense_code: k_dense_quant's arithmetic), emit the unit's words
+//   k_dense_block_deq    k_dense_deq_packed with (mn, scale) = (bmn[u], bscale[u])
+// Emission: lane l's four codes of row it are one 4 B-bit field, field f = it * 64 + l at bit 4 B f of the unit's
+// sub-stream. The wave writes its 1024 fields to its own 4 KB of LDS, then lane l builds the words l, l + 64, ... of
+// the unit (128 B of them) from the fields that overlap each — 8 / B fields where 4 B divides 32, at most 1 +
+// ceil(31 / 4 B) otherwise — and stores every word whole, consecutive lanes consecutive dwords. The stores are range-
+// checked to the unit's ceil(len B / 32) words, which lie inside its segment's [pw_s, pw_s + W_s).
+// ------------------------------------------------------------------------------------------------
+template <bool DELTA, uint32_t B, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uint64_t* __restrict__ pw,
+                                                             float* __restrict__ bmn, float* __restrict__ bscale,
+                                                             uint32_t* __restrict__ packed) {
+  constexpr uint32_t FB = 4u * B;                    // bits per field
+  constexpr uint32_t NFIELD = UNIT / 4u;             // fields per unit (1024)
+  constexpr bool ALIGNED = (32u % FB) == 0u;         // every word starts on a field (B = 1, 2, 4, 8)
+  constexpr uint32_t NF = ALIGNED ? 32u / FB : 1u + (31u + FB - 1u) / FB;  // fields that can overlap one word
+  __shared__ uint32_t sfld[WAVES][NFIELD];
+  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;  // (no block-wide barrier below: a wave owns its row of sfld)
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id(), len = U.len;
+  uint32_t* fld = sfld[threadIdx.x >> 6];
+  float4 v[UNIT_IT];
+  dense_unit_load<DELTA, DENSE_Q_AUX>(P, U, v);
+  float a = qnan(), b = qnan();
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    const uint32_t e0 = (it * 64 + lane) * 4;
+    const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x = (len == UNIT || e0 + j < len) ? xs[j] : qnan();  // (as k_dense_minmax: loads past len read 0)
+      a = fmin_nan(a, x);
+      b = fmax_nan(b, x);
+    }
+  }
+  a = wave_min(a) + 0.0f;
+  b = wave_max(b) + 0.0f;
+  const float mn = a, scale = (b == a) ? 0.0f : (b - a) / P.levels;
+  if (lane == 0) {
+    bmn[u] = mn;
+    bscale[u] = scale;
+  }
+  auto fields = [&](auto rcp_tag) {
+    constexpr bool RCP = decltype(rcp_tag)::value;
+    const float y = RCP ? 1.0f / scale : 0.0f;
+#pragma unroll
+    for (uint32_t it = 0; it < UNIT_IT; ++it) {
+      const uint32_t e0 = (it * 64 + lane) * 4;
+      const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+      uint32_t f = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t q = dense_code<RCP>(xs[j], mn, scale, y, P.levels);
+        f |= ((len == UNIT || e0 + j < len) ? q : 0u) << (j * B);  // (a code past len is 0: the padding)
+      }
+      fld[it * 64 + lane] = f;
+    }
+  };
+  if (dense_rcp_scale(scale))  // (uniform per wave, as k_dense_quant)
+    fields(std::true_type{});
+  else
+    fields(std::false_type{});
+  lds_order();
+  uint32_t nwords;
+  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
+  const __amdgpu_buffer_rsrc_t rout =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+#pragma unroll
+  for (uint32_t i = 0; i < UNIT / 32u * B / 64u; ++i) {
+    const uint32_t w = i * 64 + lane, bit = w * 32u;
+    const uint32_t f0 = bit / FB, s = ALIGNED ? 0u : bit - f0 * FB;  // the word's first field, and its bits below the word
+    uint64_t acc = fld[f0] >> s;
+    uint32_t nb = FB - s;
+#pragma unroll
+    for (uint32_t j = 1; j < NF; ++j) {
+      const uint32_t x = f0 + j < NFIELD ? fld[f0 + j] : 0u;
+      if (nb < 32u) acc |= (uint64_t)x << nb;
+      nb += FB;
+    }
+    __builtin_amdgcn_raw_buffer_store_b32((uint32_t)acc, rout, (int)(w * 4u), 0, 0);  // (past the unit's words: dropped)
+  }
+}
+
+template <uint32_t B, bool HASBASE, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_block_deq(Params P, const uint64_t* __restrict__ pw,
+                                                           const uint32_t* __restrict__ packed,
+                                                           const float* __restrict__ bmn,
+                                                           const float* __restrict__ bscale) {
+  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  dense_deq_packed_unit<B, HASBASE>(P, U, pw, packed, bmn[u], bscale[u]);
 }
 
 // k_gather: n scalars of `bytes` each, from their own storage (one device pointer each), into one contiguous
@@ -4213,6 +4327,58 @@ int coalac_decode_packed(coalac_plan_t plan, const void* d_packed, uint64_t pack
         [&](auto h, auto x) {
           hipLaunchKernelGGL((k_dense_deq_packed<b.value, h.value, x.value>), g, dim3(BLOCK), 0,
                              static_cast<hipStream_t>(stream), P, plan->dense_pw, packed);
+        },
+        d_base != nullptr, !plan->decode_latency);
+  });
+  return launched();
+}
+
+int coalac_encode_block(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                        float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, void* stream) {
+  if (!plan) return fail(COALAC_EINVAL, "coalac_encode_block: plan is NULL");
+  if ((d_in != nullptr) == (d_seg_in != nullptr))
+    return fail(COALAC_EINVAL, "coalac_encode_block: exactly one of d_in and d_seg_in must be given");
+  bool done = false;
+  int rc = dense_packed_args(plan, "coalac_encode_block", !d_bmn || !d_bscale || !d_packed, packed_bytes, &done);
+  if (rc || done) return rc;
+  if (addr_bits(d_in, d_base) & 15) return fail(COALAC_EINVAL, "coalac_encode_block: input/base must be 16-byte aligned");
+  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
+    return fail(COALAC_EINVAL, "coalac_encode_block: bmn / bscale / packed must be 4-byte aligned");
+  Params P = plan->proto;
+  P.in = d_in;
+  P.inptr = d_seg_in;
+  P.base = d_base;
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  with_code_bits((uint32_t)plan->bits, [&](auto b) {
+    with_flags(
+        [&](auto delta, auto x) {
+          hipLaunchKernelGGL((k_dense_block_quant<delta.value, b.value, x.value>), g, dim3(BLOCK), 0,
+                             static_cast<hipStream_t>(stream), P, plan->dense_pw, d_bmn, d_bscale,
+                             static_cast<uint32_t*>(d_packed));
+        },
+        d_base != nullptr, !plan->decode_latency);
+  });
+  return launched();
+}
+
+int coalac_decode_block(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_bmn,
+                        const float* d_bscale, const float* d_base, float* d_out, void* stream) {
+  bool done = false;
+  int rc = dense_packed_args(plan, "coalac_decode_block", !d_packed || !d_bmn || !d_bscale || !d_out, packed_bytes, &done);
+  if (rc || done) return rc;
+  if (addr_bits(d_packed, d_bmn, d_bscale) & 3)
+    return fail(COALAC_EINVAL, "coalac_decode_block: packed / bmn / bscale must be 4-byte aligned");
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_decode_block: output/base must be 16-byte aligned");
+  Params P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  const uint32_t* packed = static_cast<const uint32_t*>(d_packed);
+  with_code_bits((uint32_t)plan->bits, [&](auto b) {
+    with_flags(
+        [&](auto h, auto x) {
+          hipLaunchKernelGGL((k_dense_block_deq<b.value, h.value, x.value>), g, dim3(BLOCK), 0,
+                             static_cast<hipStream_t>(stream), P, plan->dense_pw, packed, d_bmn, d_bscale);
         },
         d_base != nullptr, !plan->decode_latency);
   });

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define COALAC_ABI_VERSION 8
+#define COALAC_ABI_VERSION 9
 
 enum {
   COALAC_OK = 0,
@@ -63,7 +63,9 @@ enum {
  * lossless repacking of idx / vals after an unchanged encode and before an unchanged decode; again no existing entry
  * point, plan query or workspace size changes. ABI 8 adds the bit-packed dense codes' coalac_plan_dense_packed_bytes /
  * coalac_pack_dense / coalac_unpack_dense / coalac_decode_packed — the same kind of lossless repacking for a dense
- * plan's uint8 codes (wire v4); once more nothing that existed changes.) */
+ * plan's uint8 codes (wire v4); once more nothing that existed changes. ABI 9 adds the block-wise dense pair
+ * coalac_encode_block / coalac_decode_block — one quantisation range per 4096-element unit of a dense plan, encoded in
+ * one pass into the wire v4 code stream (wire v5); every existing entry point, query and size is as it was.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -201,6 +203,32 @@ int coalac_pack_dense(coalac_plan_t plan, const void* d_vals, void* d_packed, ui
 int coalac_unpack_dense(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, void* d_vals, void* stream);
 int coalac_decode_packed(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_mn,
                          const float* d_scale, const float* d_base, float* d_out, void* stream);
+
+/* Block-wise dense quantisation (wire v5): a DENSE plan (every k == n) with bits 1..8, every 4096-element unit of it
+ * (the plan's unit table: segment by segment ceil(n / 4096) each, row after row; coalac_plan_query's n_units = U of
+ * them) quantised over its OWN range. Unit u, the u_s-th of segment s, covers the segment's elements
+ * [4096 u_s, min(n_s, 4096 (u_s + 1))), and CodecSpec v1 applies to it as if it were a segment with k = n:
+ *
+ *   bmn[u]    = the NaN-ignoring min of the unit's values (x, or x - base in delta mode), + 0.0f
+ *   bscale[u] = 0 if max == min else (max - min) / (2^bits - 1)          (max likewise NaN-ignoring, + 0.0f)
+ *   code      = coalac_encode's quantise with (bmn[u], bscale[u]);  decoded = bmn[u] + float(code) * bscale[u]
+ *               (fp32 multiply, then fp32 add; + base, fused, as coalac_decode)
+ *
+ * The codes leave and arrive as the wire v4 stream above, bit for bit its layout and length (coalac_plan_dense_packed_
+ * bytes; at 8 bits the stream is the codes): segment s owns the words [pw_s, pw_s + W_s), unit u_s starts at word
+ * pw_s + 128 b u_s, padding bits are written as zero and ignored on decode. coalac_encode_block reads the update once
+ * (no min / max pre-pass, no per-segment reduction, no byte-per-element codes) and writes bmn[U], bscale[U] and only
+ * the stream words of the plan's segments; exactly one of d_in (flat fp32[span], indexed by in_off) and d_seg_in (a
+ * DEVICE array of per-segment pointers, as coalac_encode_segptr takes) is non-NULL, d_base != NULL selects delta mode.
+ * coalac_decode_block is coalac_decode_packed with each unit's own range. Each call is one asynchronous launch on
+ * `stream`: no allocation, no workspace, no host synchronisation. COALAC_EINVAL: both or neither of d_in / d_seg_in, a
+ * sparse plan, bits == 32 (nothing to scale), a NULL pointer other than d_base, a packed_bytes below
+ * coalac_plan_dense_packed_bytes, d_in / d_base / d_out not 16-byte or d_bmn / d_bscale / d_packed not 4-byte
+ * aligned. A plan without units returns COALAC_OK and launches nothing. */
+int coalac_encode_block(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                        float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, void* stream);
+int coalac_decode_block(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_bmn,
+                        const float* d_bscale, const float* d_base, float* d_out, void* stream);
 
 /* Profiling variants: identical work, plus hipEventRecord(events[i], stream) between kernels.
  * encode: [0] before k_sample, [1] after k_sample, [2] after k_scan, [3] after the select kernels
