@@ -16,6 +16,10 @@ COALAC_FLAG_NO_FORK = 8
 COALAC_AGG_DIV = 0     # acc / total            (torch CPU division by a scalar)
 COALAC_AGG_RECIP = 1   # acc * (1.0f / total)   (torch GPU division by a host scalar)
 COALAC_AGG_SUM = 2     # acc                    (weighted_sum: the multi-GPU per-rank sum)
+COALAC_AGGD_CODES = 0   # coalac_aggregate_dense reads uint8 codes, one range per segment (wire v2 dense)
+COALAC_AGGD_PACKED = 1  # ... the wire v4 stream, one range per segment
+COALAC_AGGD_BLOCK = 2   # ... the wire v4 stream, one range per 4096-element block (wire v5)
+AGGD_DEPTH = 4          # clients whose code words k_aggregate_dense loads together (AGD_DEPTH in coalac.hip)
 
 ERRORS = {
     -1: "COALAC_EINVAL",
@@ -65,13 +69,15 @@ SIGNATURES = [
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
     ("coalac_aggregate", _I, [_P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
     ("coalac_aggregate_ev", _I, [_P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P, _P]),
+    # dense aggregate: plan, clients, kind, codes[], code_bytes, mn[], scale[], weights, total, mode, mask, base, out, stream
+    ("coalac_aggregate_dense", _I, [_P, _I, _I, _P, _U64, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
     ("coalac_gather", _I, [_P, _I, _I, _P, _P]),
     ("coalac_workspace_fallbacks", _I, [_P, _P, _P, ctypes.POINTER(_I)]),
     ("coalac_debug_stamps", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint64), _I]),
     ("coalac_debug_brackets", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _I]),
 ]
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class CodecError(RuntimeError):

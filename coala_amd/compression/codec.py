@@ -726,7 +726,37 @@ class UpdateCodec:
         return recipe.build_and_adopt(box, D, flat, raws, update.raw, device, adopt=self.recycle)
 
     # -- fused server-side aggregation ------------------------------------------------------------
-    def aggregate(self, updates, weights, template, base=None, mode="recip", device=None, params_only=False):
+    def dense_aggregate_plan(self, header, device=None):
+        """The one-layout plan whose aggregate_dense serves a round of updates with this header (aggregate(...,
+        dense_kernel=True)), or None where that route does not apply: ratio below 1, bits 32, no fp32 entries, or a
+        backend whose plans do not offer the method."""
+        sizes = _decode_layout(header["entries"]).sizes
+        if not sizes or header["ratio"] < 1.0 or header["bits"] == RAW_BITS:
+            return None
+        device = self.backend.default_device() if device is None else torch.device(device)
+        plan = self.plan_for(sizes, device, ratio=header["ratio"], bits=header["bits"])
+        return plan if getattr(plan, "aggregate_dense", None) is not None else None
+
+    def _aggregate_dense(self, plan, updates, weights, total, base_flat, mode, avg_mask, device, out):
+        """aggregate()'s fp32 entries by the dense kernel: every upload on the device in its own encoded_to() form
+        (uint8 codes, the packed stream, or a block-wise mn ... packed region; a received one through the pinned
+        staging buffer), then ONE launch over the uploads' own buffers, on the current stream."""
+        cuda = device.type == "cuda"
+        cur = torch.cuda.current_stream(device) if cuda else None
+        encs = []
+        for u in updates:
+            encs.append(u.encoded_to(device, staging=self._staging if cuda else None, plan=plan))
+            if cuda:
+                self._staged(cur)
+        kind = _dense_kind(updates[0].header, encs[0])
+        if any(_dense_kind(u.header, e) != kind for u, e in zip(updates[1:], encs[1:])):
+            raise ValueError("dense aggregation needs every upload in the same form on the device")
+        codes = [e.vals if kind == "codes" else e.packed for e in encs]
+        return plan.aggregate_dense(codes, [e.mn for e in encs], [e.scale for e in encs], weights, total=total,
+                                    base=base_flat, out=out, mode=mode, avg_mask=avg_mask, kind=kind)
+
+    def aggregate(self, updates, weights, template, base=None, mode="recip", device=None, params_only=False,
+                  dense_kernel=False):
         """Fused decode + FedAvg of several CompressedUpdates of one layout -> nn.Module (recycled from the
         decode pool once idle, as decode_module's are: a dropped earlier result is aggregated into).
 
@@ -742,6 +772,11 @@ class UpdateCodec:
         only the template's parameters are averaged (federated_averaging_only_params /
         weighted_sum_only_params, strategies.py:32-54, 93-124); every buffer keeps update 0's decoded value,
         as the reference's deepcopy(models[0]) does.
+        dense_kernel: ratio-1 updates with bits 1..8 — plain uint8 codes, bit-packed (wire v4) or
+        block-wise (wire v5) — are aggregated by the dense kernel (CodecPlan.aggregate_dense) where the backend's plan
+        offers it: every upload is read from its own encoded_to() copy, with no concatenation, no unpacking to a byte
+        per element and no implied indices, and block-wise updates are accepted. Everything else (ratio below 1, bits
+        32, a backend without the method) takes the route above, as with False.
         """
         if not updates:
             return None
@@ -759,11 +794,13 @@ class UpdateCodec:
                     (h0["ratio"], h0["bits"], h0["mode"], h0["entries"], bool(h0.get("compact")),
                      bool(h0.get("dense_packed")), bool(h0.get("blockwise"))):
                 raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode / payload format")
-        if h0.get("blockwise"):
-            raise ValueError("fused aggregation reads per-segment codes: block-wise updates are decoded one by one "
-                             "(decode_module)")
         sizes = [e["n"] for e in h0["entries"] if e["kind"] == "seg"]
         device = self.backend.default_device() if device is None else torch.device(device)
+        # the one-layout plan whose aggregate_dense reads the uploads, when this round takes that route
+        one = self.dense_aggregate_plan(h0, device) if dense_kernel else None
+        if h0.get("blockwise") and one is None:
+            raise ValueError("fused aggregation reads per-segment codes: block-wise updates are decoded one by one "
+                             "(decode_module), or aggregated by the dense kernel (dense_kernel=True)")
         base_flat = _delta_base(h0["mode"], h0["entries"], base, device,
                                 "delta-mode updates need the global model (base) to aggregate")
         state = OrderedDict()
@@ -785,7 +822,16 @@ class UpdateCodec:
                                  keep=(lambda n: n not in pnames) if params_only else None, accs=accs)
         if raw_avg is None:  # (the passthrough entries are combined one by one below: nothing to recycle into)
             recipe = sk = root = None
-        if sizes:
+        avg_mask = None
+        if sizes and params_only:
+            avg_mask = [e["name"] in pnames for e in h0["entries"] if e["kind"] == "seg"]
+        if one is not None:
+            plan = one
+            flat = self._aggregate_dense(one, updates, weights, total, base_flat, mode, avg_mask, device,
+                                         None if sk is None else sk.flat)
+            if sk is not None and flat.data_ptr() != sk.flat.data_ptr():  # a backend that returns its own buffer
+                sk = root = None
+        elif sizes:
             C = len(updates)
             plan = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"], clients=C)
             one = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"]) if h0.get("dense_packed") else None
@@ -802,9 +848,6 @@ class UpdateCodec:
             encs = [on_device(u) for u in updates]
             batched = Encoded(*(torch.cat([getattr(e, f) for e in encs]) for f in ("idx", "vals", "mn", "scale")),
                               torch.cat([e.ustart for e in encs]) if all(e.ustart is not None for e in encs) else None)
-            avg_mask = None
-            if params_only:
-                avg_mask = [e["name"] in pnames for e in h0["entries"] if e["kind"] == "seg"]
             flat = plan.aggregate(batched, weights, total=total, base=base_flat, mode=mode, avg_mask=avg_mask,
                                   out=None if sk is None else sk.flat)
             if sk is not None and flat.data_ptr() != sk.flat.data_ptr():  # a backend that returns its own buffer
@@ -836,6 +879,14 @@ class UpdateCodec:
             del state, seg_views, raw_avg
             return recipe.build_and_adopt(box, D, flat, accs, updates[0].raw, device)
         return module_with_state(template, state)
+
+
+def _dense_kind(header, enc):
+    """What CodecPlan.aggregate_dense reads of a ratio-1 upload: its block-wise stream, its bit-packed stream where
+    the upload's encoded_to() left one on the device, else its uint8 codes."""
+    if header.get("blockwise"):
+        return "block"
+    return "packed" if enc.packed is not None else "codes"
 
 
 def _aggregate_raw(updates, weights, total, mode, device, keep=None, accs=None):

@@ -647,6 +647,74 @@ class CodecPlan:
         _lib.check(rc, "coalac_aggregate")
         return out  # w / m were allocated on the launch stream: their memory is reused only after the kernel
 
+    AGG_DENSE_KINDS = {"codes": _lib.COALAC_AGGD_CODES, "packed": _lib.COALAC_AGGD_PACKED,
+                       "block": _lib.COALAC_AGGD_BLOCK}
+
+    def aggregate_dense(self, codes, mns, scales, weights, total=None, base=None, out=None, mode="recip",
+                        avg_mask=None, kind="codes", stream=None):
+        """Fused decode + FedAvg of C ratio-1 uploads of THIS plan's layout (a one-client dense plan), each read from
+        its own buffers (coalac_aggregate_dense): no concatenation, no `clients`-copies plan, no implied
+        indices. codes / mns / scales: lists of C tensors, one per upload —
+
+            kind "codes":  uint8[total_k] codes,                    mn / scale fp32[n_segments]
+            kind "packed": uint32[dense_packed_words] (wire v4),    mn / scale fp32[n_segments]
+            kind "block":  uint32[dense_packed_words],              mn / scale fp32[n_units] (wire v5: per block)
+
+        weights, total, base, mode, avg_mask and the result as aggregate(): out fp32[span] indexed by the plan's
+        segments, bit-identical to decode / decode_packed / decode_block of every upload followed by the reference's
+        weighted sum and division. The pointer arrays, the weights and the mask go up in small copies on the launch
+        stream. Asynchronous on `stream`."""
+        self._need_dense("aggregate_dense")
+        if kind not in self.AGG_DENSE_KINDS:
+            raise ValueError(f"kind must be one of {sorted(self.AGG_DENSE_KINDS)}, got {kind!r}")
+        modes = {"recip": _lib.COALAC_AGG_RECIP, "div": _lib.COALAC_AGG_DIV, "sum": _lib.COALAC_AGG_SUM}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)}, got {mode!r}")
+        C = len(codes)
+        if C < 1 or len(mns) != C or len(scales) != C or len(weights) != C:
+            raise ValueError(f"aggregate_dense: need one codes / mn / scale tensor and one weight per upload, got "
+                             f"{C} / {len(mns)} / {len(scales)} / {len(weights)}")
+        stream_kind = kind != "codes"
+        n_range = self.n_units if kind == "block" else self.n_segments
+        for i, (c, m, s) in enumerate(zip(codes, mns, scales)):
+            if stream_kind:
+                self._check_dense_packed(c, f"upload {i}: packed stream")
+            else:
+                self._check_codes(c, f"upload {i}: codes")
+            if c.data_ptr() % 4:
+                raise ValueError(f"upload {i}: the code storage must be 4-byte aligned")
+            for t in (m, s):
+                if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or \
+                        t.numel() < n_range or t.data_ptr() % 4:
+                    raise ValueError(f"upload {i}: need mn / scale as float32[{n_range}] on {self.device}, got "
+                                     f"{t.dtype}[{t.numel()}] on {t.device}")
+        if avg_mask is not None and len(avg_mask) != self.n_segments:
+            raise ValueError(f"avg_mask: need {self.n_segments} entries, got {len(avg_mask)}")
+        self._check_flat(base, "base")
+        sizes = self.table.segs
+        n_out = int((sizes[:, 0] + sizes[:, 1]).max()) if len(sizes) else 0  # (an output may end with the last segment)
+        with _on(stream):
+            if out is None:
+                out = self.empty_flat() if base is None else torch.empty_like(base)
+            # one table: the three pointer arrays, C pointers each
+            ptrs = torch.tensor([t.data_ptr() for ts in (codes, mns, scales) for t in ts],
+                                dtype=torch.int64).to(self.device)
+            w = torch.tensor([float(x) for x in weights], dtype=torch.float64).to(torch.float32).to(self.device)
+            m = None
+            if avg_mask is not None:
+                m = torch.tensor([1 if x else 0 for x in avg_mask], dtype=torch.uint8).to(self.device)
+        self._check_flat(out, "output", n_out)
+        total = float(sum(weights)) if total is None else float(total)
+        code_bytes = min(c.numel() * c.element_size() for c in codes)
+        p = ptrs.data_ptr()
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_aggregate_dense(
+                self._h, C, self.AGG_DENSE_KINDS[kind], ctypes.c_void_p(p), ctypes.c_uint64(code_bytes),
+                ctypes.c_void_p(p + 8 * C), ctypes.c_void_p(p + 16 * C), _ptr(w), ctypes.c_float(total), modes[mode],
+                _ptr(m), _ptr(base), _ptr(out), _stream_handle(stream))
+        _lib.check(rc, "coalac_aggregate_dense")
+        return out  # ptrs / w / m were allocated on the launch stream: their memory is reused only after the kernel
+
     def implied_indices(self):
         """A dense plan's indices (0..n-1 per segment, every client) as a device int32 tensor, made once."""
         t = self.__dict__.get("_implied")

@@ -340,6 +340,10 @@ class CompressionServerMixin(_CodecOwner):
             return snap[1]
 
     codec_fused_aggregate = False
+    # with codec_fused_aggregate: a round of uniform ratio-1 uploads with bits 1..8 — plain, bit-packed or block-wise —
+    # is aggregated by the dense kernel straight from the uploads' own buffers (UpdateCodec.aggregate(...,
+    # dense_kernel=True)), block-wise rounds included; off, such rounds go the ways they always went
+    codec_fused_dense_aggregate = False
 
     def _decode_upload(self, model):
         base = self._global_snapshot() if model.header["mode"] == "delta" else None
@@ -386,29 +390,31 @@ class CompressionServerMixin(_CodecOwner):
             if getattr(server_conf, "aggregation_strategy", None) == EQUAL_AVERAGE:
                 weights = [1 for _ in models]
             h0 = models[0].header
-            # (a block-wise upload has one range per block, which the fused kernel cannot read: such a round — and one of
-            # mixed formats — is decoded upload by upload below)
-            if not h0.get("blockwise") and all(
+            codec = self._codec()
+            dev = codec.backend.default_device()
+            dense = bool(self.codec_fused_dense_aggregate)
+            block = bool(h0.get("blockwise"))
+            # (a block-wise upload has one range per block, which only the dense kernel reads: without it such a round —
+            # and always one of mixed formats — is decoded upload by upload below)
+            if (not block or (dense and codec.dense_aggregate_plan(h0, dev) is not None)) and all(
                    m.header["entries"] == h0["entries"] and
                    (m.header["ratio"], m.header["bits"], m.header["mode"], bool(m.header.get("compact")),
                     bool(m.header.get("dense_packed")), bool(m.header.get("blockwise"))) ==
-                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")), bool(h0.get("dense_packed")), False)
+                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")), bool(h0.get("dense_packed")), block)
                    for m in models):
                 base = self._global_snapshot() if h0["mode"] == "delta" else None
-                codec = self._codec()
-                dev = codec.backend.default_device()
                 if distributed:
                     import torch
                     import torch.distributed as dist
                     dist.barrier()
                     sample_sum = sum(weights)  # weighted_sum returns the caller's sum (0 stays 0)
                     model = codec.aggregate(models, weights, self._real_global(), base=base, mode="sum", device=dev,
-                                            params_only=params_only)
+                                            params_only=params_only, dense_kernel=dense)
                     reduce_models(params_only)(model, torch.tensor(sample_sum).to(getattr(conf, "device", dev)))
                     return model
                 mode = "div" if dev.type == "cpu" else "recip"  # torch's division semantics on that device
                 return codec.aggregate(models, weights, self._real_global(), base=base, mode=mode, device=dev,
-                                       params_only=params_only)
+                                       params_only=params_only, dense_kernel=dense)
         models = [self._decode_upload(m) if isinstance(m, CompressedUpdate) else m for m in models]
         parent = getattr(super(), "aggregate", None)
         if parent is not None:

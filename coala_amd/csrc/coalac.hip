@@ -2509,6 +2509,15 @@ struct AggArgs {
   const uint8_t* avg_mask; // [T] 1: segment averaged, 0: client 0's value passed through; null: all averaged
 };
 
+// the end of an averaged element, one copy for k_aggregate and k_aggregate_dense: acc / total (DIV), acc * (1.0f / total)
+// (RECIP, inv_total = the fp32 quotient 1.0f / total) or acc (SUM)
+template <int MODE>
+DEV float4 agg_final(float4 a, float total, float inv_total) {
+  if (MODE == COALAC_AGG_DIV) return make_float4(a.x / total, a.y / total, a.z / total, a.w / total);
+  if (MODE == COALAC_AGG_SUM) return a;
+  return make_float4(a.x * inv_total, a.y * inv_total, a.z * inv_total, a.w * inv_total);
+}
+
 // k_aggregate: one wave per 4096-element unit of the (client-0) layout. For client i in order (segments
 // the avg mask leaves out — the buffers of aggregation_content "parameters" — take client 0's x_0 as is,
 // as strategies.weighted_sum_only_params / federated_averaging_only_params leave models[0]'s buffers,
@@ -2708,17 +2717,7 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
     float* out = P.out + U.off + e_lo;
 #pragma unroll
     for (uint32_t it = 0; it < RI; ++it) {
-      float4 o;
-      if (!avg) {
-        o = acc[it];
-      } else if (MODE == COALAC_AGG_DIV) {
-        o = make_float4(acc[it].x / A.total, acc[it].y / A.total, acc[it].z / A.total, acc[it].w / A.total);
-      } else if (MODE == COALAC_AGG_SUM) {
-        o = acc[it];
-      } else {
-        o = make_float4(acc[it].x * A.inv_total, acc[it].y * A.inv_total, acc[it].z * A.inv_total,
-                        acc[it].w * A.inv_total);
-      }
+      const float4 o = avg ? agg_final<MODE>(acc[it], A.total, A.inv_total) : acc[it];
       const uint32_t e = (it * 64 + lane) * 4;
       if (FULL) {
         *reinterpret_cast<float4*>(out + e) = o;
@@ -2946,6 +2945,27 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
   if (P.ustart_out != nullptr && lane == 0) P.ustart_out[u] = U.start;
 }
 
+// a dense plan's uint8 codes, one row of a unit at a time (shared by k_dense_deq and k_aggregate_dense): the resource over
+// the unit's `len` codes at src (loads past them return 0), lane l's four codes of row `row` as one dword — a dword load
+// where the unit's codes start and end on one (vec), else four byte loads — and their decoded values
+DEV __amdgpu_buffer_rsrc_t dense_codes_rsrc(const uint8_t* src, uint32_t len) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), (short)0, (int)len, 0x00020000);
+}
+
+DEV uint32_t dense_codes_row(__amdgpu_buffer_rsrc_t r, bool vec, uint32_t row, uint32_t lane) {
+  const uint32_t b = (row * 64 + lane) * 4;
+  if (vec) return __builtin_amdgcn_raw_buffer_load_b32(r, (int)b, 0, 0);
+  return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b, 0, 0) |
+         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 1, 0, 0) << 8) |
+         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 2, 0, 0) << 16) |
+         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 3, 0, 0) << 24);
+}
+
+DEV float4 dense_codes_values(uint32_t w, float mn, float scale) {
+  return make_float4(dequantize((uint8_t)(w & 0xFFu), mn, scale), dequantize((uint8_t)((w >> 8) & 0xFFu), mn, scale),
+                     dequantize((uint8_t)((w >> 16) & 0xFFu), mn, scale), dequantize((uint8_t)(w >> 24), mn, scale));
+}
+
 // the decoded values of a dense plan's unit (its codes sit at the positions themselves): lane l's float4 of row it
 // in d[it]; positions past the unit's end hold mn (code 0) or 0.0f (raw) and are never stored
 template <bool RAW>
@@ -2968,26 +2988,12 @@ DEV void dense_unit_values(const Params& P, const UnitDev& U, float mn, float sc
       }
     }
   } else {
-    const uint8_t* src = static_cast<const uint8_t*>(P.cvals) + o;
-    const __amdgpu_buffer_rsrc_t r =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), (short)0, (int)U.len, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r = dense_codes_rsrc(static_cast<const uint8_t*>(P.cvals) + o, U.len);
     uint32_t w[UNIT_IT];
 #pragma unroll
-    for (uint32_t it = 0; it < UNIT_IT; ++it) {
-      const uint32_t b = (it * 64 + lane) * 4;
-      if (vec) {
-        w[it] = __builtin_amdgcn_raw_buffer_load_b32(r, (int)b, 0, 0);
-      } else {
-        w[it] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b, 0, 0) |
-                ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 1, 0, 0) << 8) |
-                ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 2, 0, 0) << 16) |
-                ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 3, 0, 0) << 24);
-      }
-    }
+    for (uint32_t it = 0; it < UNIT_IT; ++it) w[it] = dense_codes_row(r, vec, it, lane);
 #pragma unroll
-    for (uint32_t it = 0; it < UNIT_IT; ++it)
-      d[it] = make_float4(dequantize((uint8_t)(w[it] & 0xFFu), mn, scale), dequantize((uint8_t)((w[it] >> 8) & 0xFFu), mn, scale),
-                          dequantize((uint8_t)((w[it] >> 16) & 0xFFu), mn, scale), dequantize((uint8_t)(w[it] >> 24), mn, scale));
+    for (uint32_t it = 0; it < UNIT_IT; ++it) d[it] = dense_codes_values(w[it], mn, scale);
   }
 }
 
@@ -3243,10 +3249,16 @@ constexpr uint32_t DPACK_E = 32;                      // entries per group: B wh
 constexpr uint32_t DPACK_G = UNIT / DPACK_E / 64;     // groups per lane per unit (2)
 
 // the unit's words inside the stream and how many it owns (the segment's last unit: up to the segment's last word)
+// (dense_unit_word_off: where they start, for a caller with one stream per client)
+template <uint32_t B>
+DEV uint64_t dense_unit_word_off(const uint64_t* pw, const UnitDev& U, uint32_t& nwords) {
+  nwords = ((uint32_t)U.len * B + 31u) >> 5;
+  return pw[U.seg] + (uint64_t)(UNIT / 32u * B) * (U.start >> UNIT_SHIFT);
+}
+
 template <uint32_t B>
 DEV const uint32_t* dense_unit_words(const uint32_t* packed, const uint64_t* pw, const UnitDev& U, uint32_t& nwords) {
-  nwords = ((uint32_t)U.len * B + 31u) >> 5;
-  return packed + pw[U.seg] + (uint64_t)(UNIT / 32u * B) * (U.start >> UNIT_SHIFT);
+  return packed + dense_unit_word_off<B>(pw, U, nwords);
 }
 
 template <uint32_t B>
@@ -3355,33 +3367,45 @@ __global__ __launch_bounds__(BLOCK) void k_unpack_dense(Params P, const uint64_t
 // loads are range-checked to the unit's own words, which lie inside its segment's W_s: a field at the end reads 0
 // past them, never another segment's word or past the stream. Same dequantize, base + x and stores as k_dense_deq.
 // (dense_deq_packed_unit: one unit of it, with the range (mn, scale) its caller read — the segment's here, the unit's
-// own in k_dense_block_deq)
+// own in k_dense_block_deq. Its pieces — the resource over a unit's words, a row's words, a row's values — are
+// k_aggregate_dense's loader too: one copy of the stream's addressing.)
+DEV __amdgpu_buffer_rsrc_t dense_words_rsrc(const uint32_t* words, uint32_t nwords) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+}
+
+template <uint32_t B>
+DEV void dense_row_words(__amdgpu_buffer_rsrc_t rin, uint32_t row, uint32_t lane, uint32_t& lo, uint32_t& hi) {
+  constexpr bool STRADDLE = (32u % (4u * B)) != 0u;
+  const uint32_t wd = ((row * 64 + lane) * 4u * B) >> 5;
+  lo = __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(wd * 4u), 0, 0);
+  hi = STRADDLE ? __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(wd * 4u + 4u), 0, 0) : 0u;
+}
+
+template <uint32_t B>
+DEV float4 dense_row_values(uint32_t lo, uint32_t hi, uint32_t row, uint32_t lane, float mn, float scale) {
+  const uint32_t sh = ((row * 64 + lane) * 4u * B) & 31u;
+  const uint32_t f = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+  constexpr uint32_t M = (1u << B) - 1u;
+  return make_float4(dequantize((uint8_t)(f & M), mn, scale), dequantize((uint8_t)((f >> B) & M), mn, scale),
+                     dequantize((uint8_t)((f >> (2 * B)) & M), mn, scale),
+                     dequantize((uint8_t)((f >> (3 * B)) & M), mn, scale));
+}
+
 template <uint32_t B, bool HASBASE>
 DEV void dense_deq_packed_unit(const Params& P, const UnitDev& U, const uint64_t* __restrict__ pw,
                                const uint32_t* __restrict__ packed, float mn, float scale) {
-  constexpr bool STRADDLE = (32u % (4u * B)) != 0u;
   const uint32_t lane = lane_id();
   uint32_t nwords;
   const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rin = dense_words_rsrc(words, nwords);
   uint32_t lo[UNIT_IT], hi[UNIT_IT];
 #pragma unroll
-  for (uint32_t it = 0; it < UNIT_IT; ++it) {
-    const uint32_t wd = ((it * 64 + lane) * 4u * B) >> 5;
-    lo[it] = __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(wd * 4u), 0, 0);
-    hi[it] = STRADDLE ? __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(wd * 4u + 4u), 0, 0) : 0u;
-  }
+  for (uint32_t it = 0; it < UNIT_IT; ++it) dense_row_words<B>(rin, it, lane, lo[it], hi[it]);
   const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
   const __amdgpu_buffer_rsrc_t rb = unit_rsrc(HASBASE ? P.base + U.off : P.out + U.off, U.len);
 #pragma unroll
   for (uint32_t it = 0; it < UNIT_IT; ++it) {
-    const uint32_t sh = ((it * 64 + lane) * 4u * B) & 31u;
-    const uint32_t f = (uint32_t)((((uint64_t)hi[it] << 32) | lo[it]) >> sh);
-    constexpr uint32_t M = (1u << B) - 1u;
-    float4 x = make_float4(dequantize((uint8_t)(f & M), mn, scale), dequantize((uint8_t)((f >> B) & M), mn, scale),
-                           dequantize((uint8_t)((f >> (2 * B)) & M), mn, scale),
-                           dequantize((uint8_t)((f >> (3 * B)) & M), mn, scale));
+    float4 x = dense_row_values<B>(lo[it], hi[it], it, lane, mn, scale);
     if (HASBASE) {
       const float4 b = unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16);
       x = make_float4(b.x + x.x, b.y + x.y, b.z + x.z, b.w + x.w);
@@ -3500,6 +3524,126 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_deq(Params P, const uint6
   if (u >= P.n_units) return;
   const UnitDev U = P.units[u];
   dense_deq_packed_unit<B, HASBASE>(P, U, pw, packed, bmn[u], bscale[u]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// dense aggregate: fused decode + FedAvg of C ratio-1 uploads of the plan's own layout, each read where
+// it lies — its uint8 codes (CODES), its wire v4 stream with one range per segment (PACKED) or per 4096-element unit
+// (BLOCK). k_aggregate's contract, element by element in client order:
+//   x_i = base + (mn_i + float(q_i) * scale_i);  acc = x_0 * w_0, acc = acc + (x_i * w_i);  out = agg_final(acc)
+// (a segment the avg mask leaves out: out = x_0). Nothing is sparse here, so there is no tile, no index, no search: the
+// accumulator and the base stay in registers, every client adds one code word (two at the straddling widths) per row
+// and lane, and the result is stored once. AGD_SPLIT waves share a unit (each owns UNIT_IT / AGD_SPLIT of its rows);
+// the code words of AGD_DEPTH clients are in flight per wave, behind one round of wave-uniform loads of those clients'
+// pointers, ranges and weights. The loaders are the decoders' own (dense_codes_row / dense_row_words), the arithmetic
+// is dequantize, the end is agg_final, the stores are k_dense_deq's.
+// ------------------------------------------------------------------------------------------------
+#ifndef AGD_SPLIT
+#define AGD_SPLIT 4
+#endif
+#ifndef AGD_DEPTH
+#define AGD_DEPTH 4
+#endif
+static_assert(AGD_SPLIT >= 1 && UNIT_IT % AGD_SPLIT == 0 && AGD_DEPTH >= 1, "dense aggregate geometry");
+
+struct AggDenseArgs {
+  const void* const* codes;   // [clients] each client's codes (uint8) or stream (uint32 words)
+  const float* const* mn;     // [clients] each client's mn / scale: one per segment, or (BLOCK) one per unit
+  const float* const* scale;
+  const float* weights;       // [clients]
+  const uint8_t* avg_mask;    // [nseg] or null, as k_aggregate's
+  uint32_t clients;
+  int mode;                   // COALAC_AGG_*: a wave-uniform branch at the end
+  uint32_t xcd;               // the XCD-aware block order (batch-sized plans, as the dense decoders')
+  float total, inv_total;
+};
+
+template <uint32_t B, int KIND, bool HASBASE>
+__global__ __launch_bounds__(BLOCK) void k_aggregate_dense(Params P, const uint64_t* __restrict__ pw, AggDenseArgs A) {
+  constexpr uint32_t RI = UNIT_IT / AGD_SPLIT, HE = UNIT / AGD_SPLIT, D = AGD_DEPTH;
+  const uint32_t lane = lane_id();
+  const uint32_t wid = __builtin_amdgcn_readfirstlane((A.xcd ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6));
+  const uint32_t u = wid / AGD_SPLIT, r0 = (wid % AGD_SPLIT) * RI;  // the unit, and the first of this wave's rows
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  if (r0 * 256u >= U.len) return;
+  static_assert(HE == RI * 256u, "rows per wave");
+  const uint32_t ri = KIND == COALAC_AGGD_BLOCK ? u : U.seg;  // the element's range: its unit's or its segment's
+  const bool avg = A.avg_mask == nullptr || A.avg_mask[U.seg] != 0;
+  const uint32_t ncl = avg ? A.clients : 1u;
+  const uint64_t o = U.out_off + U.start;  // CODES: the unit's first code (k == n: entry e is element e)
+  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;
+  uint32_t nwords = 0;
+  const uint64_t woff = KIND == COALAC_AGGD_CODES ? 0 : dense_unit_word_off<B>(pw, U, nwords);
+  const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
+  float4 bv[RI], acc[RI];
+  if (HASBASE) {
+    const __amdgpu_buffer_rsrc_t rb = unit_rsrc(P.base + U.off, U.len);
+#pragma unroll
+    for (uint32_t it = 0; it < RI; ++it) bv[it] = unit_load_x4<false>(rb, rb, ((r0 + it) * 64 + lane) * 16);
+  }
+  // acc starts at -0.0f, the exact additive identity, so no client is special (as k_aggregate)
+#pragma unroll
+  for (uint32_t it = 0; it < RI; ++it) acc[it] = make_float4(-0.0f, -0.0f, -0.0f, -0.0f);
+  for (uint32_t c0 = 0; c0 < ncl; c0 += D) {
+    // round 1, wave-uniform: the clients' pointers, ranges and weights (a chunk's tail repeats the last client: every
+    // load stays inside some client's buffers, and the repeats are not accumulated)
+    const void* cp[D];
+    float mn[D], sc[D], w[D];
+#pragma unroll
+    for (uint32_t t = 0; t < D; ++t) {
+      const uint32_t c = min(c0 + t, ncl - 1);
+      cp[t] = A.codes[c];
+      mn[t] = A.mn[c][ri];
+      sc[t] = A.scale[c][ri];
+      w[t] = avg ? A.weights[c] : 1.0f;  // (x_0 * 1.0f == x_0)
+    }
+    // round 2: every code word of the chunk
+    uint32_t lo[D][RI], hi[D][RI];
+#pragma unroll
+    for (uint32_t t = 0; t < D; ++t) {
+      if (KIND == COALAC_AGGD_CODES) {
+        const __amdgpu_buffer_rsrc_t rin = dense_codes_rsrc(static_cast<const uint8_t*>(cp[t]) + o, U.len);
+#pragma unroll
+        for (uint32_t it = 0; it < RI; ++it) {
+          lo[t][it] = dense_codes_row(rin, vec, r0 + it, lane);
+          hi[t][it] = 0u;
+        }
+      } else {
+        const __amdgpu_buffer_rsrc_t rin = dense_words_rsrc(static_cast<const uint32_t*>(cp[t]) + woff, nwords);
+#pragma unroll
+        for (uint32_t it = 0; it < RI; ++it) dense_row_words<B>(rin, r0 + it, lane, lo[t][it], hi[t][it]);
+      }
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < D; ++t) {
+      if (c0 + t >= ncl) break;
+#pragma unroll
+      for (uint32_t it = 0; it < RI; ++it) {
+        float4 x = KIND == COALAC_AGGD_CODES ? dense_codes_values(lo[t][it], mn[t], sc[t])
+                                             : dense_row_values<B>(lo[t][it], hi[t][it], r0 + it, lane, mn[t], sc[t]);
+        if (HASBASE) x = make_float4(bv[it].x + x.x, bv[it].y + x.y, bv[it].z + x.z, bv[it].w + x.w);
+        const float4 p = make_float4(x.x * w[t], x.y * w[t], x.z * w[t], x.w * w[t]);
+        acc[it] = make_float4(acc[it].x + p.x, acc[it].y + p.y, acc[it].z + p.z, acc[it].w + p.w);
+      }
+    }
+  }
+  auto store = [&](auto fin) {
+#pragma unroll
+    for (uint32_t it = 0; it < RI; ++it) {
+      const float4 v = fin(acc[it]);
+      if ((U.len & 3u) == 0)
+        unit_store_x4<STORE_AUX>(rout, ((r0 + it) * 64 + lane) * 16, v);
+      else
+        unit_store_x1x4<STORE_AUX>(rout, ((r0 + it) * 64 + lane) * 16, v);
+    }
+  };
+  if (!avg || A.mode == COALAC_AGG_SUM)
+    store([&](float4 a) { return a; });
+  else if (A.mode == COALAC_AGG_DIV)
+    store([&](float4 a) { return agg_final<COALAC_AGG_DIV>(a, A.total, A.inv_total); });
+  else
+    store([&](float4 a) { return agg_final<COALAC_AGG_RECIP>(a, A.total, A.inv_total); });
 }
 
 // k_gather: n scalars of `bytes` each, from their own storage (one device pointer each), into one contiguous
@@ -4456,6 +4600,64 @@ int coalac_aggregate(coalac_plan_t plan, int clients, const int32_t* d_idx, cons
                      const uint8_t* d_avg_mask, const float* d_base, float* d_out, void* stream) {
   return coalac_aggregate_ev(plan, clients, d_idx, d_vals, d_mn, d_scale, d_ustart, d_weights, total, mode, d_avg_mask,
                              d_base, d_out, stream, nullptr);
+}
+
+int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void* const* d_codes, uint64_t code_bytes,
+                           const float* const* d_mn, const float* const* d_scale, const float* d_weights, float total,
+                           int mode, const uint8_t* d_avg_mask, const float* d_base, float* d_out, void* stream) {
+  const char* who = "coalac_aggregate_dense";
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse round is coalac_aggregate's", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to dequantise", who);
+  if (clients < 1) return fail(COALAC_EINVAL, "%s: clients=%d, need at least 1", who, clients);
+  if (kind != COALAC_AGGD_CODES && kind != COALAC_AGGD_PACKED && kind != COALAC_AGGD_BLOCK)
+    return fail(COALAC_EINVAL, "%s: bad kind %d", who, kind);
+  if (mode != COALAC_AGG_DIV && mode != COALAC_AGG_RECIP && mode != COALAC_AGG_SUM)
+    return fail(COALAC_EINVAL, "%s: bad mode %d", who, mode);
+  if (!d_codes || !d_mn || !d_scale || !d_weights || !d_out) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  const uint64_t need = kind == COALAC_AGGD_CODES ? plan->total_k : 4 * plan->dense_words;
+  if (code_bytes < need)
+    return fail(COALAC_EINVAL, "%s: code_bytes=%llu < the plan's %llu", who, (unsigned long long)code_bytes,
+                (unsigned long long)need);
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "%s: output/base must be 16-byte aligned", who);
+  if (addr_bits(d_codes, d_mn, d_scale) & 7 || addr_bits(d_weights) & 3)
+    return fail(COALAC_EINVAL, "%s: the pointer arrays must be 8-byte, the weights 4-byte aligned", who);
+  if (plan->proto.n_units == 0) return COALAC_OK;
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  AggDenseArgs A{};
+  A.codes = d_codes;
+  A.mn = d_mn;
+  A.scale = d_scale;
+  A.weights = d_weights;
+  A.avg_mask = d_avg_mask;
+  A.clients = (uint32_t)clients;
+  A.mode = mode;
+  A.xcd = !plan->decode_latency;
+  A.total = total;
+  A.inv_total = 1.0f / total;
+  const dim3 g(ceil_div(P.n_units * (uint32_t)AGD_SPLIT, WAVES));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  with_flags(
+      [&](auto hb) {
+        if (kind == COALAC_AGGD_CODES) {
+          hipLaunchKernelGGL((k_aggregate_dense<8, COALAC_AGGD_CODES, hb.value>), g, dim3(BLOCK), 0, st, P, plan->dense_pw, A);
+          return;
+        }
+        with_code_bits((uint32_t)plan->bits, [&](auto b) {
+          if (kind == COALAC_AGGD_PACKED)
+            hipLaunchKernelGGL((k_aggregate_dense<b.value, COALAC_AGGD_PACKED, hb.value>), g, dim3(BLOCK), 0, st, P,
+                               plan->dense_pw, A);
+          else
+            hipLaunchKernelGGL((k_aggregate_dense<b.value, COALAC_AGGD_BLOCK, hb.value>), g, dim3(BLOCK), 0, st, P,
+                               plan->dense_pw, A);
+        });
+      },
+      d_base != nullptr);
+  return launched();
 }
 
 int coalac_gather(const void* const* d_src, int n, int elem_bytes, void* d_out, void* stream) {

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define COALAC_ABI_VERSION 9
+#define COALAC_ABI_VERSION 10
 
 enum {
   COALAC_OK = 0,
@@ -65,7 +65,9 @@ enum {
  * coalac_pack_dense / coalac_unpack_dense / coalac_decode_packed — the same kind of lossless repacking for a dense
  * plan's uint8 codes (wire v4); once more nothing that existed changes. ABI 9 adds the block-wise dense pair
  * coalac_encode_block / coalac_decode_block — one quantisation range per 4096-element unit of a dense plan, encoded in
- * one pass into the wire v4 code stream (wire v5); every existing entry point, query and size is as it was.) */
+ * one pass into the wire v4 code stream (wire v5); every existing entry point, query and size is as it was. ABI 10 adds
+ * the one entry point coalac_aggregate_dense — the fused decode + FedAvg of ratio-1 uploads read from their own uint8
+ * codes, wire v4 streams or block-wise (wire v5) streams; nothing that existed changes.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -271,6 +273,37 @@ int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, c
                         const float* d_mn, const float* d_scale, const uint32_t* d_ustart, const float* d_weights,
                         float total, int mode, const uint8_t* d_avg_mask, const float* d_base, float* d_out,
                         void* stream, void* const* events);
+
+/* Fused decode + FedAvg of `clients` ratio-1 (dense) uploads, each read where it lies. `plan` is a
+ * ONE-LAYOUT dense plan (every k == n, bits 1..8): the layout is the plan's own table, and d_out / d_base are indexed by
+ * its in_off. Per element of every segment, in client order — coalac_aggregate's contract, bit for bit:
+ *   x_i = d_base + decoded_i (without a base: decoded_i);  decoded_i = mn + float(q_i) * scale (fp32 multiply, then add)
+ *   acc = x_0 * w_0;  acc = acc + (x_i * w_i), i = 1..clients-1 (fp32, no FMA);  d_out = acc / total | acc * (1.0f /
+ *   total) | acc by `mode` (COALAC_AGG_DIV | RECIP | SUM); a segment whose d_avg_mask byte is 0 gets d_out = x_0.
+ * So the result equals coalac_decode / coalac_decode_packed / coalac_decode_block of every upload followed by the
+ * reference's weighted_sum and division (coala/server/strategies.py:6-29, 57-90), without the `clients` dense copies.
+ * kind says what client i's buffers hold:
+ *   COALAC_AGGD_CODES   d_codes[i]: uint8 codes, entry e of segment s at out_off_s + e (wire v2 dense); mn / scale fp32[nseg]
+ *   COALAC_AGGD_PACKED  d_codes[i]: the wire v4 stream of the plan (coalac_pack_dense's layout);     mn / scale fp32[nseg]
+ *   COALAC_AGGD_BLOCK   d_codes[i]: the same stream; mn / scale fp32[n_units], one pair per 4096-element unit (wire v5,
+ *                       coalac_encode_block's bmn / bscale)
+ * d_codes, d_mn, d_scale: DEVICE arrays of `clients` device pointers (as coalac_encode_segptr takes d_seg_in): every
+ * upload stays where it was copied to — no concatenation, no batched `clients`-copies plan, no implied indices.
+ * code_bytes: the length of EACH client's code buffer, at least total_k (CODES) or coalac_plan_dense_packed_bytes (the
+ * stream kinds). d_weights: DEVICE fp32[clients]; total: float(sum of the weights); d_avg_mask: DEVICE uint8[nseg] or
+ * NULL (every segment averaged). Only the segments' elements of d_out are written. One asynchronous launch on `stream`:
+ * no allocation, no workspace, no host synchronisation; any `clients` >= 1.
+ * COALAC_EINVAL (with a coalac_last_error message): a sparse plan, bits == 32, clients < 1, a bad kind or mode, a NULL
+ * pointer other than d_base / d_avg_mask, a code_bytes below the above, d_out / d_base not 16-byte aligned. A plan
+ * without units returns COALAC_OK and launches nothing. The CONTENTS of the three pointer arrays live on the device and
+ * cannot be checked here: every d_codes[i] must be 4-byte aligned and code_bytes long, every d_mn[i] / d_scale[i] hold
+ * nseg (BLOCK: n_units) floats — the caller's duty (coala_amd/compression/plan.py aggregate_dense checks each tensor). An
+ * untrusted stream can mis-decode but not make the kernel read outside [d_codes[i], d_codes[i] + code_bytes): loads are
+ * range-checked to each unit's own codes or words, and padding bits are ignored. */
+enum { COALAC_AGGD_CODES = 0, COALAC_AGGD_PACKED = 1, COALAC_AGGD_BLOCK = 2 };
+int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void* const* d_codes, uint64_t code_bytes,
+                           const float* const* d_mn, const float* const* d_scale, const float* d_weights, float total,
+                           int mode, const uint8_t* d_avg_mask, const float* d_base, float* d_out, void* stream);
 
 /* Snapshot n scalars of elem_bytes (1, 2, 4 or 8) each, read through the DEVICE pointer array d_src (each pointer
  * aligned to elem_bytes), into the contiguous d_out, in one launch on `stream`: the passthrough entries of an
