@@ -125,41 +125,35 @@ class CompressedUpdate:
         """A compact carrier's packed entry stream (wire.py, version 3), or a dense-packed carrier's bit-packed code
         stream (version 4), as a uint32 tensor; else None. Packed on the GPU right after the encode where the plan can
         (CodecPlan.pack / pack_dense); otherwise on the host, on first use (a received carrier: its blob's section)."""
-        if self.header.get("dense_packed") or self.header.get("blockwise"):
-            if self._packed[0] is None:
-                blob = self._blob[0]
-                if blob is not None:
-                    o, n = wire.sections(blob, self.header)[1]["packed"]
-                    words = np.frombuffer(blob, dtype="<u4", count=n // 4, offset=o).copy()
-                else:
-                    words = wire.pack_dense_codes(_to_host(self.encoded.vals)[0], self._seg_sizes(), self.header["bits"])
-                self._packed[0] = torch.from_numpy(words)
-            return self._packed[0]
-        if not self.header.get("compact"):
+        stream, bits = wire.format_of(self.header).stream, self.header["bits"]
+        if stream is None:
             return None
         if self._packed[0] is None:
-            idx, vals = _to_host(self.encoded.idx, self.encoded.vals)
-            self._packed[0] = torch.from_numpy(wire.pack_entries(idx, vals, self.header["bits"]))
+            blob = self._blob[0]
+            if stream == "entries":
+                words = wire.pack_entries(*_to_host(self.encoded.idx, self.encoded.vals), bits)
+            elif blob is not None:
+                o, n = wire.sections(blob, self.header)[1]["packed"]
+                words = np.frombuffer(blob, dtype="<u4", count=n // 4, offset=o).copy()
+            else:
+                words = wire.pack_dense_codes(_to_host(self.encoded.vals)[0], self._seg_sizes(), bits)
+            self._packed[0] = torch.from_numpy(words)
         return self._packed[0]
 
     def _seg_sizes(self):
         return _decode_layout(self.header["entries"]).sizes
 
+    @property
+    def signature(self):
+        """(ratio, bits, mode, wire version): what updates must share, next to their layout, to be aggregated as one."""
+        h = self.header
+        return h["ratio"], h["bits"], h["mode"], wire.format_of(h).version
+
     # -- size accounting (client/base.py:155, 474-487) -------------------------------------------
     @property
     def nbytes(self):
-        h = self.header
-        vb = 4 if h["bits"] == RAW_BITS else 1
-        ib = 0 if h["ratio"] >= 1.0 else 4  # ratio 1: indices implied, not shipped (wire.py "dense")
-        raw_b = _raw_nbytes(self.raw)
-        if h.get("blockwise"):  # mn, scale per block and the bit-packed code stream
-            return 8 * h["n_blocks"] + 4 * wire.dense_packed_words(self._seg_sizes(), h["bits"]) + raw_b
-        if h.get("dense_packed"):  # mn, scale and the bit-packed code stream
-            return 8 * h["n_segments"] + 4 * wire.dense_packed_words(self._seg_sizes(), h["bits"]) + raw_b
-        if h.get("compact"):  # the packed stream, and the values only as fp32
-            return (8 * h["n_segments"] + 4 * wire.packed_words(h["total_k"], h["bits"])
-                    + (4 * h["total_k"] if h["bits"] == RAW_BITS else 0) + 4 * h["n_units"] + raw_b)
-        return 8 * h["n_segments"] + (ib + vb) * h["total_k"] + 4 * h.get("n_units", 0) + raw_b
+        """The payload's bytes: its array sections (wire.section_list) and the raw passthrough entries."""
+        return sum(n * dt.itemsize for _, dt, n in wire.section_list(self.header)) + _raw_nbytes(self.raw)
 
     def parameters(self):
         """One meta tensor whose numel * 32 bit equals the payload size, so the reference's
@@ -178,6 +172,7 @@ class CompressedUpdate:
         rawb = raw.entry_bytes() if isinstance(raw, RawState) else {
             n: (t.cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes() if t.numel() else b"")
             for n, t in raw.items()}
+        wh = dict(h, dense=True) if wire.is_dense(h) else h  # the header as the blob spells it
 
         def header_json():
             entries, pos = [], 0
@@ -187,33 +182,19 @@ class CompressedUpdate:
                     e = dict(e, off=pos, nbytes=nb)
                     pos += nb
                 entries.append(e)
-            return wire.encode_header(dict(h, entries=entries, **({"dense": True} if h["ratio"] >= 1.0 else {})))
-        # the header (with each raw entry's blob offset) depends on the layout and the raw byte counts only
-        hjson = _PACKED_HEADERS.get(h["entries"], (h["ratio"], h["bits"], h["mode"], h["n_segments"], h.get("total_k"),
-                                                   h.get("n_units"), tuple(map(len, rawb.values())),
-                                                   bool(h.get("compact")), bool(h.get("dense_packed")),
-                                                   h.get("blockwise"), h.get("n_blocks")), header_json)
+            return wire.encode_header(dict(wh, entries=entries))
+        # its JSON (with each raw entry's blob offset) depends on the layout and the raw byte counts only
+        hjson = _PACKED_HEADERS.get(h["entries"], (self.signature, h["n_segments"], h.get("total_k"), h.get("n_units"),
+                                                   h.get("n_blocks"), tuple(map(len, rawb.values()))), header_json)
+        # ONE device-to-host copy, of the buffers the format ships (wire.section_list) and no other: where a packed
+        # stream travels, idx and the uint8 codes stay where they are
         enc = self.encoded
+        names = [name for name, _, _ in wire.section_list(h)]
+        arrs = dict(zip(names, _to_host(*(self.packed.to(enc.mn.device) if name == "packed" else getattr(enc, name)
+                                          for name in names))))
         rawbytes = b"".join(rawb[e["name"]] for e in h["entries"] if e["kind"] == "raw")
-        if h.get("blockwise"):  # wire v5: the per-block ranges and the stream — nothing else is copied
-            arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device))
-            return wire.pack({"dense": True, "blockwise": h["blockwise"], "n_blocks": h["n_blocks"]}, arrs[0], arrs[1],
-                             None, None, rawbytes, header_json=hjson, packed=arrs[2])
-        if h.get("dense_packed"):  # wire v4: the bit-packed stream instead of the uint8 codes, which are not copied
-            arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device))
-            return wire.pack({"dense": True, "dense_packed": True}, arrs[0], arrs[1], None, None, rawbytes,
-                             header_json=hjson, packed=arrs[2])
-        if h.get("compact"):  # wire v3: the packed stream instead of idx and the uint8 codes, neither copied
-            f32 = h["bits"] == RAW_BITS
-            arrs = _to_host(enc.mn, enc.scale, self.packed.to(enc.mn.device), enc.ustart, *((enc.vals,) if f32 else ()))
-            return wire.pack({"compact": True, "n_units": h["n_units"]}, arrs[0], arrs[1], None,
-                             arrs[4] if f32 else None, rawbytes, header_json=hjson, ustart=arrs[3], packed=arrs[2])
-        v2 = "n_units" in h  # wire v2: the per-unit starts ride along
-        arrs = _to_host(enc.mn, enc.scale, enc.idx, enc.vals, *((enc.ustart,) if v2 else ()))
-        pack_h = {"dense": h["ratio"] >= 1.0}
-        if v2:
-            pack_h["n_units"] = h["n_units"]
-        return wire.pack(pack_h, *arrs[:4], rawbytes, header_json=hjson, ustart=arrs[4] if v2 else None)
+        return wire.pack(wh, arrs["mn"], arrs["scale"], arrs.get("idx"), arrs.get("vals"), rawbytes, header_json=hjson,
+                         ustart=arrs.get("ustart"), packed=arrs.get("packed"))
 
     def encoded_to(self, device, staging=None, plan=None):
         """The encoded buffers on `device`. An unpickled update (the server side of a remote upload,
@@ -223,66 +204,58 @@ class CompressedUpdate:
         blob's region (mn ... ustart) holds the packed stream: idx / vals are then materialised on the device by
         `plan`.unpack (the decoding plan of this update; without one, the host-unpacked buffers are copied). A
         dense-packed blob (wire v4) for a plan that decodes the stream (decode_packed): its mn ... packed region, the
-        stream staying packed on the device (_dense_packed_to); a block-wise blob (wire v5) likewise, always: its
-        decode (decode_block) reads nothing but the stream."""
+        stream staying packed on the device; a block-wise blob (wire v5) likewise, always: its decode (decode_block)
+        reads nothing but the stream."""
         device = torch.device(device)
-        blob = self._blob[0]
-        compact = bool(self.header.get("compact"))
-        if self.header.get("blockwise"):
-            return self._dense_packed_to(device, staging if device.type == "cuda" else None)
-        if self.header.get("dense_packed") and device.type == "cuda" and getattr(plan, "decode_packed", None) is not None:
-            return self._dense_packed_to(device, staging)
-        if (staging is None or device.type != "cuda" or blob is None or self.header.get("dense")
-                or self.encoded.idx.device == device or (compact and getattr(plan, "unpack", None) is None)):
-            return self.encoded.to(device, non_blocking=True)
-        _, sec = wire.sections(blob, self.header)
-        lo = sec["mn"][0]
-        last = sec["ustart"] if "ustart" in sec else sec["vals"]
-        hi = last[0] + last[1]
-        stage = staging(hi - lo)
-        stage[:hi - lo].numpy()[:] = np.frombuffer(blob, dtype=np.uint8, count=hi - lo, offset=lo)
-        K = int(self.header["total_k"])
-        room = (hi - lo + 15) // 16 * 16  # a compact blob: idx (and the uint8 codes) are unpacked behind the region
-        f32 = self.header["bits"] == RAW_BITS
-        dev = torch.empty(room + (4 * K + (0 if f32 else K) if compact else 0), dtype=torch.uint8, device=device)
-        dev[:hi - lo].copy_(stage[:hi - lo], non_blocking=True)
+        cuda, blob, enc = device.type == "cuda", self._blob[0], self.encoded
+        fmt = wire.format_of(self.header)
+        if fmt.stream == "dense" and (fmt.per_block or (cuda and getattr(plan, "decode_packed", None) is not None)):
+            # for a plan that reads the stream: an Encoded whose `packed` is the bit-packed stream on `device`, with no
+            # uint8 codes there (vals None: CodecPlan.unpack_dense makes them for who needs them); a carrier whose
+            # buffers are on the device already is handed out as it is
+            if enc.mn.device == device:
+                return Encoded(enc.idx, enc.vals, enc.mn, enc.scale, None, self.packed.to(device, non_blocking=True))
+            no_idx = torch.empty(0, dtype=torch.int32, device=device)
+            if blob is None or staging is None or not cuda:
+                return Encoded(no_idx, None, enc.mn.to(device, non_blocking=True),
+                               enc.scale.to(device, non_blocking=True), None, self.packed.to(device, non_blocking=True))
+            view, _ = self._staged_sections(device, staging)
+            return Encoded(no_idx, None, view("mn", torch.float32), view("scale", torch.float32), None,
+                           view("packed", torch.uint32))
+        compact = fmt.stream == "entries"
+        if (staging is None or not cuda or blob is None or wire.is_dense(self.header)
+                or enc.idx.device == device or (compact and getattr(plan, "unpack", None) is None)):
+            return enc.to(device, non_blocking=True)
+        K, f32 = int(self.header["total_k"]), self.header["bits"] == RAW_BITS
         vdt = torch.float32 if f32 else torch.uint8
-
-        def view(name, dt):
-            o, n = sec[name]
-            return dev[o - lo:o - lo + n].view(dt)
+        # a compact blob: idx (and the uint8 codes) are unpacked behind the region
+        view, room = self._staged_sections(device, staging, 4 * K + (0 if f32 else K) if compact else 0)
+        mn, scale, ustart = view("mn", torch.float32), view("scale", torch.float32), view("ustart", torch.int32)
         if compact:
-            idx = dev[room:room + 4 * K].view(torch.int32)
-            vals = view("vals", vdt) if f32 else dev[room + 4 * K:room + 5 * K]
-            ustart = view("ustart", torch.int32)
+            idx = room[:4 * K].view(torch.int32)
+            vals = view("vals", vdt) if f32 else room[4 * K:]
             plan.unpack(view("packed", torch.uint32), ustart, out=(idx, vals))
-            return Encoded(idx, vals, view("mn", torch.float32), view("scale", torch.float32), ustart)
-        return Encoded(view("idx", torch.int32), view("vals", vdt), view("mn", torch.float32),
-                       view("scale", torch.float32), view("ustart", torch.int32) if "ustart" in sec else None)
+            return Encoded(idx, vals, mn, scale, ustart)
+        return Encoded(view("idx", torch.int32), view("vals", vdt), mn, scale, ustart)
 
-    def _dense_packed_to(self, device, staging):
-        """encoded_to of a dense-packed (or block-wise) carrier for a plan that reads the stream: an Encoded whose `packed` is the
-        bit-packed stream on `device`. A received carrier moves ONE pinned host-to-device copy of its blob's mn ...
-        packed region and has no uint8 codes there (vals None: CodecPlan.unpack_dense makes them for who needs them);
-        a carrier whose buffers are on the device already is handed out as it is."""
-        enc, blob = self.encoded, self._blob[0]
-        if enc.mn.device == device:
-            return Encoded(enc.idx, enc.vals, enc.mn, enc.scale, None, self.packed.to(device, non_blocking=True))
-        if blob is None or staging is None:
-            return Encoded(torch.empty(0, dtype=torch.int32, device=device), None, enc.mn.to(device, non_blocking=True),
-                           enc.scale.to(device, non_blocking=True), None, self.packed.to(device, non_blocking=True))
-        _, sec = wire.sections(blob, self.header)
-        lo, hi = sec["mn"][0], sec["packed"][0] + sec["packed"][1]
-        stage = staging(hi - lo)
-        stage[:hi - lo].numpy()[:] = np.frombuffer(blob, dtype=np.uint8, count=hi - lo, offset=lo)
-        dev = torch.empty(hi - lo, dtype=torch.uint8, device=device)
-        dev.copy_(stage[:hi - lo], non_blocking=True)
+    def _staged_sections(self, device, staging, room=0):
+        """ONE host-to-device copy of the blob's array sections (they lie back to back: wire.sections) through the pinned
+        buffer staging(nbytes) into one allocation on `device`, with `room` more bytes behind them (16-byte aligned) ->
+        (view(name, torch dtype): that section there, or None where the format has none; the room)."""
+        blob = self._blob[0]
+        sec = wire.sections(blob, self.header)[1]
+        lo, (o, n) = sec["mn"][0], sec[next(reversed(sec))]
+        size = o + n - lo
+        stage = staging(size)
+        stage[:size].numpy()[:] = np.frombuffer(blob, dtype=np.uint8, count=size, offset=lo)
+        behind = (size + 15) // 16 * 16
+        dev = torch.empty(behind + room, dtype=torch.uint8, device=device)
+        dev[:size].copy_(stage[:size], non_blocking=True)
 
         def view(name, dt):
-            o, n = sec[name]
-            return dev[o - lo:o - lo + n].view(dt)
-        return Encoded(torch.empty(0, dtype=torch.int32, device=device), None, view("mn", torch.float32),
-                       view("scale", torch.float32), None, view("packed", torch.uint32))
+            o, n = sec.get(name, (None, 0))
+            return None if o is None else dev[o - lo:o - lo + n].view(dt)
+        return view, dev[behind:]
 
     @classmethod
     def from_bytes(cls, blob):
@@ -643,7 +616,7 @@ class UpdateCodec:
         decode_module): decode into its flat buffer and copy the passthrough entries into its raw buffers
         instead of allocating — state is then None."""
         h = update.header  # self-describing: decode with the blob's own ratio/bits/mode
-        D = _decode_layout(h["entries"])
+        D, fmt = _decode_layout(h["entries"]), wire.format_of(h)
         flat = plan = None
         raw = update.raw
         if D.sizes:
@@ -663,25 +636,16 @@ class UpdateCodec:
                 with torch.cuda.stream(side):
                     enc = update.encoded_to(device, staging=self._staging, plan=plan)
                     self._staged(side)
-                    if h.get("blockwise"):  # per-block ranges: its own decode, from the bit stream
-                        flat = plan.decode_block(enc.packed, enc.mn, enc.scale, base=base_flat, out=out, stream=side)
-                    elif enc.packed is not None:  # a dense-packed update: decoded from the bit stream itself
-                        flat = plan.decode_packed(enc.packed, enc.mn, enc.scale, base=base_flat, out=out, stream=side)
-                    else:
-                        flat = plan.decode(enc, base=base_flat, out=out, stream=side)
+                    flat = _decode_encoded(plan, fmt, enc, base_flat, out, side)
                     if into is not None:
                         _copy_raw_groups(raw, into, non_blocking=True)
                 cur.wait_stream(side)
             else:
                 if into is not None:
                     _reuse_after(into, None, None)
-                if h.get("blockwise"):
-                    enc = update.encoded_to(device)
-                    flat = plan.decode_block(enc.packed, enc.mn, enc.scale, base=base_flat,
-                                             out=None if into is None else into.flat)
-                else:
-                    enc = update.encoded.to(device, non_blocking=True)
-                    flat = plan.decode(enc, base=base_flat, out=None if into is None else into.flat)
+                # (off the GPU only a block-wise update is read from its stream: a dense-packed one decodes from its codes)
+                enc = update.encoded_to(device) if fmt.per_block else update.encoded.to(device, non_blocking=True)
+                flat = _decode_encoded(plan, fmt, enc, base_flat, None if into is None else into.flat)
                 if into is not None:
                     _copy_raw_groups(raw, into)
         elif into is not None:
@@ -786,19 +750,14 @@ class UpdateCodec:
         if len(weights) != len(updates):
             raise ValueError("one weight per update")
         total = sum(weights)
-        h0 = updates[0].header
-        for u in updates[1:]:
-            h = u.header
-            if (h["ratio"], h["bits"], h["mode"], h["entries"], bool(h.get("compact")), bool(h.get("dense_packed")),
-                    bool(h.get("blockwise"))) != \
-                    (h0["ratio"], h0["bits"], h0["mode"], h0["entries"], bool(h0.get("compact")),
-                     bool(h0.get("dense_packed")), bool(h0.get("blockwise"))):
-                raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode / payload format")
+        h0, fmt = updates[0].header, wire.format_of(updates[0].header)
+        if not _uniform(updates):
+            raise ValueError("fused aggregation needs updates of one layout / ratio / bits / mode / payload format")
         sizes = [e["n"] for e in h0["entries"] if e["kind"] == "seg"]
         device = self.backend.default_device() if device is None else torch.device(device)
         # the one-layout plan whose aggregate_dense reads the uploads, when this round takes that route
         one = self.dense_aggregate_plan(h0, device) if dense_kernel else None
-        if h0.get("blockwise") and one is None:
+        if fmt.per_block and one is None:
             raise ValueError("fused aggregation reads per-segment codes: block-wise updates are decoded one by one "
                              "(decode_module), or aggregated by the dense kernel (dense_kernel=True)")
         base_flat = _delta_base(h0["mode"], h0["entries"], base, device,
@@ -834,7 +793,7 @@ class UpdateCodec:
         elif sizes:
             C = len(updates)
             plan = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"], clients=C)
-            one = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"]) if h0.get("dense_packed") else None
+            one = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"]) if fmt.stream == "dense" else None
             unpack = getattr(one, "unpack_dense", None)
 
             def on_device(u):
@@ -884,9 +843,26 @@ class UpdateCodec:
 def _dense_kind(header, enc):
     """What CodecPlan.aggregate_dense reads of a ratio-1 upload: its block-wise stream, its bit-packed stream where
     the upload's encoded_to() left one on the device, else its uint8 codes."""
-    if header.get("blockwise"):
+    if wire.format_of(header).per_block:
         return "block"
     return "packed" if enc.packed is not None else "codes"
+
+
+def _uniform(updates):
+    """Updates of one layout, ratio, bits, mode and payload format: what one fused aggregation takes."""
+    u0 = updates[0]
+    return all(u.signature == u0.signature and u.header["entries"] == u0.header["entries"] for u in updates[1:])
+
+
+def _decode_encoded(plan, fmt, enc, base, out, stream=None):
+    """The plan's decode of an update in the form encoded_to() left it in: a block-wise update from its stream with
+    each block's own range, a dense-packed one whose stream is on the device from the stream itself, else from its
+    idx / vals."""
+    if fmt.per_block:
+        return plan.decode_block(enc.packed, enc.mn, enc.scale, base=base, out=out, stream=stream)
+    if enc.packed is not None:
+        return plan.decode_packed(enc.packed, enc.mn, enc.scale, base=base, out=out, stream=stream)
+    return plan.decode(enc, base=base, out=out, stream=stream)
 
 
 def _aggregate_raw(updates, weights, total, mode, device, keep=None, accs=None):

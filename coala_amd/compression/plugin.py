@@ -66,7 +66,8 @@ import threading
 
 from torch import nn
 
-from .codec import CompressedUpdate, UpdateCodec
+from . import wire
+from .codec import CompressedUpdate, UpdateCodec, _uniform
 from .download import CompressedModel, compress_model
 from .state import _layout_walk, _module_walk
 
@@ -393,15 +394,10 @@ class CompressionServerMixin(_CodecOwner):
             codec = self._codec()
             dev = codec.backend.default_device()
             dense = bool(self.codec_fused_dense_aggregate)
-            block = bool(h0.get("blockwise"))
+            block = wire.format_of(h0).per_block
             # (a block-wise upload has one range per block, which only the dense kernel reads: without it such a round —
             # and always one of mixed formats — is decoded upload by upload below)
-            if (not block or (dense and codec.dense_aggregate_plan(h0, dev) is not None)) and all(
-                   m.header["entries"] == h0["entries"] and
-                   (m.header["ratio"], m.header["bits"], m.header["mode"], bool(m.header.get("compact")),
-                    bool(m.header.get("dense_packed")), bool(m.header.get("blockwise"))) ==
-                   (h0["ratio"], h0["bits"], h0["mode"], bool(h0.get("compact")), bool(h0.get("dense_packed")), block)
-                   for m in models):
+            if (not block or (dense and codec.dense_aggregate_plan(h0, dev) is not None)) and _uniform(models):
                 base = self._global_snapshot() if h0["mode"] == "delta" else None
                 if distributed:
                     import torch

@@ -4,6 +4,7 @@ import numpy as np
 
 from ._cache import IdentityCache
 from .spec import UNIT, VALID_BITS, SegmentTable, k_for
+from .wire import check_header, is_dense
 
 MODES = ("delta", "weights")
 
@@ -21,13 +22,8 @@ def validate(header, idx, ustart=None):
     ns_rep, first, units = _VALIDATED.get(
         header["entries"], (float(header["ratio"]), int(header["n_segments"]), int(header["total_k"])),
         lambda: _validate_layout(header))
-    if "blockwise" in header:  # wire v5: one range per 4096-element block of the header's own layout
-        if not header.get("dense") or int(header["blockwise"]) != UNIT:
-            raise ValueError("COALAQ1: a block-wise update is dense, in blocks of 4096")
-        if int(header.get("n_blocks", -1)) != sum((int(e["n"]) + UNIT - 1) // UNIT
-                                                  for e in header["entries"] if e["kind"] == "seg"):
-            raise ValueError("COALAQ1: block count does not match the layout")
-    if header.get("dense"):  # implied indices (0..n-1 per segment): nothing to check beyond the layout
+    check_header(header, on_wire=True)  # its format's own rules (wire v5: one range per block of this layout)
+    if is_dense(header, on_wire=True):  # implied indices (0..n-1 per segment): nothing to check beyond the layout
         if idx.size != 0 or ustart is not None:
             raise ValueError("COALAQ1: a dense update carries no indices or starts")
         return

@@ -66,14 +66,21 @@ Version 5, BLOCK-WISE DENSE QUANTISATION (opt-in, "dense" updates with bits 1..8
     (also at bits 8, where it is simply the codes): the same W_s, pw_s, field order and zero padding, so a block starts
     at word pw_s + 128*b*u_s. The blob is 8 U + 4 P + raw payload bytes (plus header and alignment). unpack() returns
     mn / scale of length U and the rebuilt uint8 codes. block_count / block_table below are the block order on the host.
+
+The executable form of the above is the table FORMATS below: one record per version with the version's ordered
+sections (name, dtype, element count) and its header rules. format_of(header) picks the record — nothing else in the
+package reads the format keys — and is_dense(header) says whether the indices are implied. pack, sections and unpack are
+one walk each over section_list(header), so they cannot disagree on a layout; CompressedUpdate (codec.py) takes its byte
+count, the buffers it ships and its staging region from the same list.
 """
 import json
 import struct
 import threading
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
+from ._cache import IdentityCache
 from .spec import RAW_BITS, UNIT, VALID_BITS, k_for
 
 MAGIC = b"COALAQ1\0"
@@ -237,8 +244,15 @@ def unpack_dense_codes(packed, sizes, bits, out_off=None, out=None):
     return out
 
 
+_SIZES = IdentityCache(64)  # entries list -> its fp32 segment sizes (headers of one layout share the list)
+
+
+def _entry_sizes(entries):
+    return [int(e["n"]) for e in entries if e["kind"] == "seg"]
+
+
 def _seg_sizes(header):
-    return [int(e["n"]) for e in header["entries"] if e["kind"] == "seg"]
+    return _SIZES.get(header["entries"], (), _entry_sizes, header["entries"])
 
 
 def block_count(sizes):
@@ -257,86 +271,155 @@ def block_table(sizes):
     return np.asarray(rows, dtype=np.int64).reshape(-1, 2)
 
 
-def _check_blockwise(header, layout=True):
-    """The header rules of a block-wise (version 5) payload; returns (segment sizes, U). layout=False: the format keys
-    only (pack() is handed a header that may hold nothing else; the full header travels as header_json)."""
-    if not header.get("dense"):
+# -- the format table -----------------------------------------------------------------------------------------------
+# One record per wire version: what travels between the JSON header and the raw bytes, and what a header of that
+# version must say. sections(header, dense) -> the ordered [(name, numpy dtype, element count)]; rules(header, dense,
+# layout) raises ValueError (None: no rules of its own; layout False: the format keys only, for pack(), whose header
+# may hold no entries to check counts against). stream: what the "packed" section holds ("entries": version 3's
+# fields, "dense": version 4's code stream, None: there is none); per_block: mn / scale hold one entry per block.
+Format = namedtuple("Format", "version stream per_block sections rules")
+_F4, _U4, _I4, _U1 = np.dtype("<f4"), np.dtype("<u4"), np.dtype("<i4"), np.dtype("u1")
+
+
+def _ranges(count):
+    return [("mn", _F4, count), ("scale", _F4, count)]
+
+
+def _v1_sections(h, dense):
+    K = int(h["total_k"])
+    return _ranges(int(h["n_segments"])) + [("idx", _I4, 0 if dense else K),
+                                            ("vals", _F4 if int(h["bits"]) == RAW_BITS else _U1, K)]
+
+
+def _v2_sections(h, dense):
+    return _v1_sections(h, dense) + [("ustart", _I4, int(h["n_units"]))]
+
+
+def _v3_sections(h, dense):
+    K, bits = int(h["total_k"]), int(h["bits"])
+    return (_ranges(int(h["n_segments"])) + [("packed", _U4, packed_words(K, bits))]
+            + ([("vals", _F4, K)] if bits == RAW_BITS else []) + [("ustart", _I4, int(h["n_units"]))])
+
+
+def _code_stream(h):
+    return ("packed", _U4, dense_packed_words(_seg_sizes(h), h["bits"]))
+
+
+def _v4_sections(h, dense):
+    return _ranges(int(h["n_segments"])) + [_code_stream(h)]
+
+
+def _v5_sections(h, dense):
+    return _ranges(int(h["n_blocks"])) + [_code_stream(h)]
+
+
+def _need_code_bits(h, layout, widest, what):
+    """bits in 1..widest; a header without bits passes only where the layout is not checked (layout=False)."""
+    if (layout or "bits" in h) and not 1 <= int(h.get("bits", 0)) <= widest:
+        raise ValueError(f"COALAQ1: {what} codes are 1..{widest} bits wide, not {h.get('bits')}")
+
+
+def _v3_rules(h, dense, layout):
+    if dense or "n_units" not in h:
+        raise ValueError("COALAQ1: a compact payload is sparse and carries its per-unit starts (\"n_units\")")
+    if layout and (h.get("bits") not in VALID_BITS or int(h["total_k"]) < 0):
+        raise ValueError("COALAQ1: bad compact header")
+
+
+def _v4_rules(h, dense, layout):
+    if not dense or h.get("compact") or "n_units" in h:
+        raise ValueError("COALAQ1: a dense-packed payload needs \"dense\" and excludes \"compact\" and per-unit starts")
+    _need_code_bits(h, layout, 7, "dense-packed")
+
+
+def _v5_rules(h, dense, layout):
+    if not dense:
         raise ValueError("COALAQ1: \"blockwise\" needs a \"dense\" payload")
-    if isinstance(header["blockwise"], bool) or int(header["blockwise"]) != UNIT:
-        raise ValueError(f"COALAQ1: block size {header['blockwise']!r} (only {UNIT} is defined)")
-    if header.get("dense_packed") or header.get("compact") or "n_units" in header:
+    if isinstance(h["blockwise"], bool) or int(h["blockwise"]) != UNIT:
+        raise ValueError(f"COALAQ1: block size {h['blockwise']!r} (only {UNIT} is defined)")
+    if h.get("dense_packed") or h.get("compact") or "n_units" in h:
         raise ValueError("COALAQ1: \"blockwise\" excludes \"dense_packed\", \"compact\" and per-unit starts")
-    if "bits" in header and not 1 <= int(header["bits"]) <= 8:
-        raise ValueError(f"COALAQ1: block-wise codes are 1..8 bits wide, not {header['bits']}")
-    if not layout:
-        return None, int(header.get("n_blocks", -1))
-    if "bits" not in header:
-        raise ValueError("COALAQ1: header without bits")
-    ns = _seg_sizes(header)
-    if sum(ns) != int(header["total_k"]):
-        raise ValueError("COALAQ1: dense header with k != n")
-    if "n_blocks" not in header or int(header["n_blocks"]) != block_count(ns):
+    _need_code_bits(h, layout, 8, "block-wise")
+    if layout and int(h.get("n_blocks", -1)) != block_count(_seg_sizes(h)):
         raise ValueError("COALAQ1: header n_blocks is not the layout's block count")
-    return ns, int(header["n_blocks"])
+
+
+FORMATS = (Format(VERSION, None, False, _v1_sections, None),
+           Format(VERSION_2, None, False, _v2_sections, None),
+           Format(VERSION_3, "entries", False, _v3_sections, _v3_rules),
+           Format(VERSION_4, "dense", False, _v4_sections, _v4_rules),
+           Format(VERSION_5, "dense", True, _v5_sections, _v5_rules))
+
+
+def format_of(header):
+    """The Format a header describes: the one place that reads the format keys, in their order of precedence."""
+    if "blockwise" in header:
+        return FORMATS[4]
+    if header.get("dense_packed"):
+        return FORMATS[3]
+    if header.get("compact"):
+        return FORMATS[2]
+    return FORMATS[1] if "n_units" in header else FORMATS[0]
+
+
+def is_dense(header, on_wire=False):
+    """Implied indices (0..n-1 per segment, an empty idx section). A header in a blob says so itself ("dense": true);
+    a carrier's in-memory header (UpdateCodec._encode) has no such key and is dense at ratio 1. on_wire: the header
+    is one read from, or written into, a blob, where the key alone counts: a ratio-1 blob without it ships its
+    indices (the payloads of before the key existed)."""
+    return bool(header.get("dense")) or (not on_wire and header.get("ratio", 0.0) >= 1.0)
+
+
+def section_list(header, on_wire=False):
+    """The ordered (name, numpy dtype, element count) of every array section of a payload with this header, between
+    the JSON header and the raw bytes: the layouts of the module docstring, stated once."""
+    return format_of(header).sections(header, is_dense(header, on_wire))
+
+
+def check_header(header, on_wire=False):
+    """The header rules of the header's format, counts checked against its entries (ValueError)."""
+    fmt, dense = format_of(header), is_dense(header, on_wire)
+    if fmt.rules is not None:
+        fmt.rules(header, dense, True)
+    if dense and int(header["total_k"]) != sum(_seg_sizes(header)):
+        raise ValueError("COALAQ1: dense header with k != n")
+
+
+def _section_offsets(secs, pos):
+    """([(name, dtype, count, byte offset)], offset of the raw bytes) of a section_list behind a header that ends at
+    byte pos: every section, and the raw bytes, at the next 16-byte boundary."""
+    out = []
+    for name, dt, n in secs:
+        pos += _pad16(pos)
+        out.append((name, dt, n, pos))
+        pos += n * dt.itemsize
+    return out, pos + _pad16(pos)
 
 
 def pack(header, mn, scale, idx, vals, raw, header_json=None, ustart=None, packed=None):
-    """numpy arrays + raw bytes -> blob (bytes). A "dense" header drops idx (it is implied). header_json: the
-    header's JSON encoding, if the caller has it already. ustart: the per-unit starts (version 2; the header
-    must then carry "n_units" = len(ustart)). packed: the packed entry stream (version 3, which needs ustart and a
-    header with "compact": true): it stands where idx stood, and vals is the fp32 values at bits 32, else None.
-    A header with "dense" and "dense_packed" (version 4): packed is the bit-packed dense stream, the only section
-    after mn and scale (idx, vals and ustart are not written). A header with "blockwise" (version 5): mn / scale hold
-    one entry per block ("n_blocks" of them) and packed is the same stream."""
-    if header.get("blockwise"):
-        _, U = _check_blockwise(header, layout=False)
-        if packed is None or ustart is not None or len(mn) != U or len(scale) != U:
-            raise ValueError("COALAQ1: a block-wise payload needs the packed stream and one mn / scale per block")
-        return _pack_stream(VERSION_5, header, header_json, mn, scale, packed, raw)
-    if header.get("dense_packed"):
-        if not header.get("dense") or packed is None or ustart is not None or "n_units" in header:
-            raise ValueError("COALAQ1: a dense-packed payload needs \"dense\", the packed stream and no per-unit starts")
-        return _pack_stream(VERSION_4, header, header_json, mn, scale, packed, raw)
-    if header.get("dense"):
-        idx = np.zeros(0, dtype=np.int32)
-    if (ustart is not None) != ("n_units" in header) or (ustart is not None and len(ustart) != header["n_units"]):
-        raise ValueError("COALAQ1: ustart section and header n_units disagree")
-    if (packed is not None) != bool(header.get("compact")) or (packed is not None and ustart is None):
-        raise ValueError("COALAQ1: a compact payload needs the packed stream, the per-unit starts and \"compact\"")
+    """numpy arrays + raw bytes -> blob (bytes): the sections the header's format lists (section_list), each taken from
+    the argument of its name, which must hold as many elements as the header says; arguments the format has no section
+    for are ignored (idx and uint8 vals next to a packed stream), except that ustart and packed must be None then. A
+    "dense" header's idx is implied and not written. header_json: the header's JSON encoding, if the caller has it
+    already; `header` then needs only what names the format and counts its sections."""
+    fmt, dense = format_of(header), is_dense(header, on_wire=True)
+    if fmt.rules is not None:  # (layout=False, the format keys only: this header may hold no entries to count)
+        fmt.rules(header, dense, False)
     h = header_json if header_json is not None else encode_header(header)
-    ver = VERSION_3 if packed is not None else VERSION if ustart is None else VERSION_2
-    parts = [MAGIC, struct.pack("<II", ver, len(h)), h]
-    size = 16 + len(h)
-    arrays = [np.ascontiguousarray(mn, "<f4"), np.ascontiguousarray(scale, "<f4")]
-    if packed is not None:
-        arrays.append(np.ascontiguousarray(packed, "<u4"))
-        if vals is not None:
-            arrays.append(np.ascontiguousarray(vals, "<f4"))
-    else:
-        arrays += [np.ascontiguousarray(idx, "<i4"), np.ascontiguousarray(vals)]
-    if ustart is not None:
-        arrays.append(np.ascontiguousarray(ustart, "<i4"))
-    for arr in arrays:
-        p = _pad16(size)
-        parts.append(b"\0" * p)
-        b = arr.tobytes()
-        parts.append(b)
-        size += p + len(b)
-    p = _pad16(size)
-    parts.append(b"\0" * p)
-    parts.append(bytes(raw))
-    return b"".join(parts)
-
-
-def _pack_stream(ver, header, header_json, mn, scale, packed, raw):
-    """mn | scale | packed | raw, each 16-byte aligned, behind the header: the layout versions 4 and 5 share."""
-    h = header_json if header_json is not None else encode_header(header)
-    parts, size = [MAGIC, struct.pack("<II", ver, len(h)), h], 16 + len(h)
-    for arr in (np.ascontiguousarray(mn, "<f4"), np.ascontiguousarray(scale, "<f4"), np.ascontiguousarray(packed, "<u4")):
-        b = arr.tobytes()
-        parts += [b"\0" * _pad16(size), b]
-        size += _pad16(size) + len(b)
-    parts += [b"\0" * _pad16(size), bytes(raw)]
+    given = {"mn": mn, "scale": scale, "idx": idx, "vals": vals, "ustart": ustart, "packed": packed}
+    secs, end = _section_offsets(fmt.sections(header, dense), 16 + len(h))
+    names = [s[0] for s in secs]
+    if (ustart is not None and "ustart" not in names) or (packed is not None and "packed" not in names):
+        raise ValueError("COALAQ1: per-unit starts or a packed stream where the header describes none")
+    parts, size = [MAGIC, struct.pack("<II", fmt.version, len(h)), h], 16 + len(h)
+    for name, dt, n, off in secs:
+        implied = given[name] is None or (name == "idx" and n == 0)  # (a dense header: whatever idx holds stays home)
+        arr = np.zeros(0, dt) if implied else np.ascontiguousarray(given[name], dt).reshape(-1)
+        if arr.size != n:
+            raise ValueError(f"COALAQ1: section {name} holds {arr.size} elements, the header says {n}")
+        parts += [b"\0" * (off - size), arr.tobytes()]
+        size = off + arr.nbytes
+    parts += [b"\0" * (end - size), bytes(raw)]
     return b"".join(parts)
 
 
@@ -365,120 +448,49 @@ def encode_header(header):
     return json.dumps(header, separators=(",", ":"), sort_keys=True).encode()
 
 
-def sections(blob, header=None):
-    """(header, {name: (byte offset, byte count)}) of the mn / scale / idx / vals (/ ustart) sections in `blob` — a
-    compact or dense-packed blob: `packed` where idx (and the uint8 codes) stood — which lie back to back (each
-    16-byte aligned): one host-to-device copy moves all of them."""
+def _open(blob, header=None):
+    """(memoryview, version word, header, end of the header) of a blob; header: parsed already (the caller's own)."""
     mv = memoryview(blob)
     if bytes(mv[:8]) != MAGIC:
         raise ValueError("not a COALAQ1 blob (bad magic)")
     ver, hl = struct.unpack_from("<II", mv, 8)
-    if header is None:
-        header = _parse_header(mv, hl)
-    T, K = int(header["n_segments"]), int(header["total_k"])
-    bits = int(header["bits"])
-    vsz = 4 if bits == RAW_BITS else 1
-    pos = 16 + hl
-    out = {}
-    if header.get("blockwise"):  # version 5: per-block ranges, then version 4's stream
-        U = int(header["n_blocks"])
-        names = [("mn", 4 * U), ("scale", 4 * U), ("packed", 4 * dense_packed_words(_seg_sizes(header), bits))]
-    elif header.get("dense_packed"):  # version 4: the bit-packed dense stream, nothing else
-        names = [("mn", 4 * T), ("scale", 4 * T), ("packed", 4 * dense_packed_words(_seg_sizes(header), bits))]
-    elif header.get("compact"):  # version 3: the packed stream where idx stood; the values only as fp32
-        names = [("mn", 4 * T), ("scale", 4 * T), ("packed", 4 * packed_words(K, bits))]
-        if bits == RAW_BITS:
-            names.append(("vals", 4 * K))
-    else:
-        names = [("mn", 4 * T), ("scale", 4 * T), ("idx", 0 if header.get("dense") else 4 * K), ("vals", vsz * K)]
-    if "n_units" in header:
-        names.append(("ustart", 4 * int(header["n_units"])))
-    for name, n in names:
-        pos += _pad16(pos)
-        out[name] = (pos, n)
-        pos += n
-    return header, out
+    return mv, ver, _parse_header(mv, hl) if header is None else header, 16 + hl
 
 
-def _unpack_blockwise(mv, pos, header):
-    """unpack() of a version-5 blob: mn / scale per block, the uint8 codes rebuilt from the stream."""
-    ns, U = _check_blockwise(header)
-    bits = int(header["bits"])
-    out = []
-    for dt, n in ((np.dtype("<f4"), U), (np.dtype("<f4"), U), (np.dtype("<u4"), dense_packed_words(ns, bits))):
-        pos += _pad16(pos)
-        if pos + n * dt.itemsize > len(mv):
-            raise ValueError("COALAQ1: truncated blob")
-        out.append(np.frombuffer(mv, dtype=dt, count=n, offset=pos))
-        pos += n * dt.itemsize
-    pos += _pad16(pos)
-    return (header, out[0], out[1], np.zeros(0, dtype="<i4"), unpack_dense_codes(out[2], ns, bits), bytes(mv[pos:]), None)
+def sections(blob, header=None):
+    """(header, {name: (byte offset, byte count)}) of the array sections in `blob`, in blob order (section_list): they
+    lie back to back, each 16-byte aligned, so one host-to-device copy moves all of them. header: the blob's own,
+    parsed already, or its carrier's in-memory one (CompressedUpdate.header)."""
+    mv, _, h, pos = _open(blob, header)
+    return h, {name: (off, n * dt.itemsize) for name, dt, n, off in _section_offsets(section_list(h, header is None), pos)[0]}
 
 
 def unpack(blob):
     """blob -> (header dict, mn, scale, idx, vals, raw bytes, ustart or None). Arrays are read-only views of
     blob; a "dense" blob's idx is empty (implied). A compact (version 3) blob's idx and uint8 vals are rebuilt
-    from its packed stream (unpack_entries, with every segment's k = k_for(n, ratio) as validate() expects). A
-    block-wise (version 5) blob's mn / scale have one entry per block."""
-    mv = memoryview(blob)
-    if bytes(mv[:8]) != MAGIC:
-        raise ValueError("not a COALAQ1 blob (bad magic)")
-    ver, hl = struct.unpack_from("<II", mv, 8)
-    if ver not in (VERSION, VERSION_2, VERSION_3, VERSION_4, VERSION_5):
-        raise ValueError(f"unsupported COALAQ1 version {ver}")
-    header = _parse_header(mv, hl)
-    if (ver == VERSION_5) != ("blockwise" in header):
-        raise ValueError("COALAQ1: version and header blockwise disagree")
-    if ver == VERSION_5:
-        return _unpack_blockwise(mv, 16 + hl, header)
-    compact = ver == VERSION_3
-    if compact != bool(header.get("compact")):
-        raise ValueError("COALAQ1: version and header compact disagree")
-    if (ver in (VERSION_2, VERSION_3)) != ("n_units" in header):
-        raise ValueError("COALAQ1: version and header n_units disagree")
-    dense_packed = ver == VERSION_4
-    if dense_packed != bool(header.get("dense_packed")):
-        raise ValueError("COALAQ1: version and header dense_packed disagree")
-    T, K = int(header["n_segments"]), int(header["total_k"])
-    bits = int(header["bits"])
-    vdt = np.dtype("<f4") if bits == RAW_BITS else np.dtype("u1")
-    pos = 16 + hl
-    out = []
-    dense = bool(header.get("dense"))
-    if dense_packed:
-        if not dense or not 1 <= bits <= 7 or K < 0:
-            raise ValueError("COALAQ1: bad dense_packed header (needs \"dense\" and bits 1..7)")
-        ns = _seg_sizes(header)
-        if sum(ns) != K:
-            raise ValueError("COALAQ1: dense header with k != n")
-        layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<u4"), dense_packed_words(ns, bits))]
-    elif compact:
-        if dense or bits not in VALID_BITS or K < 0:
-            raise ValueError("COALAQ1: bad compact header")
-        layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<u4"), packed_words(K, bits)),
-                  (vdt, K if bits == RAW_BITS else 0)]
-    else:
-        layout = [(np.dtype("<f4"), T), (np.dtype("<f4"), T), (np.dtype("<i4"), 0 if dense else K), (vdt, K)]
-    if ver in (VERSION_2, VERSION_3):
-        layout.append((np.dtype("<i4"), int(header["n_units"])))
-    for dt, n in layout:
-        pos += _pad16(pos)
-        if n < 0 or pos + n * dt.itemsize > len(mv):
+    from its packed stream (unpack_entries, with every segment's k = k_for(n, ratio) as validate() expects), a
+    version-4 / 5 blob's uint8 codes from its own (unpack_dense_codes). A block-wise (version 5) blob's mn / scale
+    have one entry per block."""
+    mv, ver, header, pos = _open(blob)
+    fmt = format_of(header)
+    if fmt.version != ver:
+        raise ValueError(f"COALAQ1: version word {ver}, but the header's keys (\"blockwise\", \"dense_packed\", "
+                         f"\"compact\", \"n_units\") describe version {fmt.version}")
+    check_header(header, on_wire=True)
+    secs, raw_at = _section_offsets(section_list(header, on_wire=True), pos)
+    out = {}
+    for name, dt, n, off in secs:
+        if n < 0 or off + n * dt.itemsize > len(mv):
             raise ValueError("COALAQ1: truncated blob")
-        out.append(np.frombuffer(mv, dtype=dt, count=n, offset=pos))
-        pos += n * dt.itemsize
-    pos += _pad16(pos)
-    raw = bytes(mv[pos:])
-    if dense and K != sum(int(e["n"]) for e in header["entries"] if e["kind"] == "seg"):
-        raise ValueError("COALAQ1: dense header with k != n")
-    if dense_packed:  # the uint8 codes, rebuilt: what a version-1 dense blob carries
-        return (header, out[0], out[1], np.zeros(0, dtype="<i4"), unpack_dense_codes(out[2], ns, bits), raw, None)
-    ustart = out[4] if ver != VERSION else None
-    if compact:
-        ns = [int(e["n"]) for e in header["entries"] if e["kind"] == "seg"]
+        out[name] = np.frombuffer(mv, dtype=dt, count=n, offset=off)
+    idx, vals, bits = out.get("idx"), out.get("vals"), int(header["bits"])
+    if fmt.stream == "entries":
+        ns = _seg_sizes(header)
         ks = [k_for(n, float(header["ratio"])) for n in ns]
-        if sum(ks) != K:
+        if sum(ks) != int(header["total_k"]):
             raise ValueError("COALAQ1: kept-entry count mismatch")
-        idx, codes = unpack_entries(out[2], ustart, ns, ks, bits)
-        out[2], out[3] = idx, (out[3] if bits == RAW_BITS else codes)
-    return (header, *out[:4], raw, ustart)
+        idx, codes = unpack_entries(out["packed"], out["ustart"], ns, ks, bits)
+        vals = vals if bits == RAW_BITS else codes
+    elif fmt.stream == "dense":  # the uint8 codes, rebuilt: what a version-1 dense blob carries
+        idx, vals = np.zeros(0, dtype="<i4"), unpack_dense_codes(out["packed"], _seg_sizes(header), bits)
+    return header, out["mn"], out["scale"], idx, vals, bytes(mv[raw_at:]), out.get("ustart")
