@@ -451,27 +451,34 @@ class CodecPlan:
         _lib.check(rc, "coalac_unpack_dense")
         return out
 
-    def decode_packed(self, packed, mn, scale, base=None, out=None, stream=None):
-        """decode() of a dense plan straight from the bit-packed stream (coalac_decode_packed: no byte-per-element
-        intermediate) -> dense flat fp32[span] (+ base, fused); bit-identical to unpack_dense followed by decode.
-        Asynchronous on `stream`."""
-        self._need_dense("decode_packed")
-        self._check_dense_packed(packed, "packed stream")
-        for t in (mn, scale):
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or \
-                    t.numel() < self.n_segments:
-                raise ValueError(f"decode_packed: need mn / scale as float32[{self.n_segments}] on {self.device}, got "
+    def _check_ranges(self, who, n, names, *ts):
+        for t in ts:
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+                raise ValueError(f"{who}: need {names} as float32[{n}] on {self.device}, got "
                                  f"{t.dtype}[{t.numel()}] on {t.device}")
+
+    def _decode_stream(self, fn, who, n, names, packed, r0, r1, base, out, stream):
+        # decode_packed / decode_block: one call of fn, the ranges (r0, r1: `names`, n of each) one per segment or unit
+        self._need_dense(who)
+        self._check_dense_packed(packed, "packed stream")
+        self._check_ranges(who, n, names, r0, r1)
         self._check_flat(base, "base")
         with _on(stream):
             if out is None:
                 out = self.empty_flat() if base is None else torch.empty_like(base)
         self._check_flat(out, "output")
         with _device_ctx(self.device):
-            rc = self._lib.coalac_decode_packed(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(mn),
-                                                _ptr(scale), _ptr(base), _ptr(out), _stream_handle(stream))
-        _lib.check(rc, "coalac_decode_packed")
+            rc = fn(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(r0), _ptr(r1), _ptr(base),
+                    _ptr(out), _stream_handle(stream))
+        _lib.check(rc, fn.__name__)
         return out
+
+    def decode_packed(self, packed, mn, scale, base=None, out=None, stream=None):
+        """decode() of a dense plan straight from the bit-packed stream (coalac_decode_packed: no byte-per-element
+        intermediate) -> dense flat fp32[span] (+ base, fused); bit-identical to unpack_dense followed by decode.
+        Asynchronous on `stream`."""
+        return self._decode_stream(self._lib.coalac_decode_packed, "decode_packed", self.n_segments, "mn / scale",
+                                   packed, mn, scale, base, out, stream)
 
     # -- block-wise dense quantisation (wire v5) --------------------------------------------------
     def empty_block_encoded(self):
@@ -482,13 +489,6 @@ class CodecPlan:
         buf = torch.empty(2 * a + 4 * P, dtype=torch.uint8, device=self.device)
         return (buf[:4 * U].view(torch.float32), buf[a:a + 4 * U].view(torch.float32),
                 buf[2 * a:2 * a + 4 * P].view(torch.uint32))
-
-    def _check_block_ranges(self, who, *ts):
-        for t in ts:
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or \
-                    t.numel() < self.n_units:
-                raise ValueError(f"{who}: need bmn / bscale as float32[{self.n_units}] on {self.device}, got "
-                                 f"{t.dtype}[{t.numel()}] on {t.device}")
 
     def encode_block(self, flat=None, tensors=None, base=None, out=None, stream=None, checked=False, ptrs=None):
         """Block-wise encode of a dense plan (coalac_encode_block): every 4096-element unit quantised over its own
@@ -510,7 +510,7 @@ class CodecPlan:
             with _on(stream):
                 out = self.empty_block_encoded()
         bmn, bscale, packed = out
-        self._check_block_ranges("encode_block", bmn, bscale)
+        self._check_ranges("encode_block", self.n_units, "bmn / bscale", bmn, bscale)
         self._check_dense_packed(packed, "packed output")
         with _device_ctx(self.device):
             rc = self._lib.coalac_encode_block(self._h, x, seg, _ptr(base), _ptr(bmn), _ptr(bscale), _ptr(packed),
@@ -521,19 +521,8 @@ class CodecPlan:
     def decode_block(self, packed, bmn, bscale, base=None, out=None, stream=None):
         """Decode of a block-wise stream (coalac_decode_block: decode_packed with each unit's own range) -> dense flat
         fp32[span] (+ base, fused). Asynchronous on `stream`."""
-        self._need_dense("decode_block")
-        self._check_dense_packed(packed, "packed stream")
-        self._check_block_ranges("decode_block", bmn, bscale)
-        self._check_flat(base, "base")
-        with _on(stream):
-            if out is None:
-                out = self.empty_flat() if base is None else torch.empty_like(base)
-        self._check_flat(out, "output")
-        with _device_ctx(self.device):
-            rc = self._lib.coalac_decode_block(self._h, _ptr(packed), ctypes.c_uint64(4 * packed.numel()), _ptr(bmn),
-                                               _ptr(bscale), _ptr(base), _ptr(out), _stream_handle(stream))
-        _lib.check(rc, "coalac_decode_block")
-        return out
+        return self._decode_stream(self._lib.coalac_decode_block, "decode_block", self.n_units, "bmn / bscale",
+                                   packed, bmn, bscale, base, out, stream)
 
     def unit_starts(self, idx, stream=None):
         """The per-unit starts (wire v2) of this plan's idx list, computed on the device for a payload that carries

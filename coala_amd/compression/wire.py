@@ -51,7 +51,7 @@ Version 4, BIT-PACKED DENSE CODES (opt-in, "dense" updates with bits 1..7 only; 
     untrusted stream can mis-decode but cannot produce an out-of-range code. At bits 8 the stream would be as long as
     the codes and at bits 32 there are none: neither is ever packed, and a header that says so is rejected.
     dense_packed_words / pack_dense_codes / unpack_dense_codes below are this format on the host (numpy); the GPU's
-    k_pack_dense / k_unpack_dense / k_dense_deq_packed (coalac.hip) produce and read the same bytes. unpack() of a
+    k_pack_dense / k_unpack_dense / k_dense_deq_stream (coalac.hip) produce and read the same bytes. unpack() of a
     version-4 blob returns the rebuilt uint8 codes, so validate() and every consumer of codes sees what it sees for
     a version-1 / 2 dense blob.
 

@@ -531,6 +531,15 @@ DEV float dequantize(uint8_t q, float mn, float scale) {
   return mn + p;
 }
 
+// The range of CodecSpec v1 from the kept values' NaN-ignoring min a and max b: each + 0.0f (a canonical zero), mn = a,
+// scale = one level's share of b - a, or 0 when they are equal. The one copy: every encoder's mn / scale is this op sequence.
+DEV void codec_range(float a, float b, float levels, float& mn, float& scale) {
+  a = a + 0.0f;
+  b = b + 0.0f;
+  mn = a;
+  scale = (b == a) ? 0.0f : (b - a) / levels;
+}
+
 template <bool RAW>
 DEV void store_val(const Params& P, uint64_t o, float v, float mn, float scale) {
   if (RAW)
@@ -581,10 +590,12 @@ DEV int band_shift(uint32_t tlo, uint32_t thi, int bin_bits = 11) {
   return bl > bin_bits ? bl - bin_bits : 0;
 }
 
-// Buffer resource over n fp32 elements at p (gfx9 word 3; loads at byte offsets >= 4n return 0).
-DEV __amdgpu_buffer_rsrc_t unit_rsrc(const float* p, uint32_t n) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), (short)0, (int)(n * 4u), 0x00020000);
+// Buffer resource over `bytes` bytes at p (gfx9 word 3): a load at a byte offset >= bytes returns 0, a store there is
+// dropped. unit_rsrc: over n fp32 elements.
+DEV __amdgpu_buffer_rsrc_t bytes_rsrc(const void* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
 }
+DEV __amdgpu_buffer_rsrc_t unit_rsrc(const float* p, uint32_t n) { return bytes_rsrc(p, n * 4u); }
 
 // non-temporal 16-byte buffer load (aux bit 1 = nt on gfx94x/gfx950) of x (or x - base) at byte offset
 template <bool DELTA>
@@ -1006,10 +1017,7 @@ DEV void small_encode(const Params& P, uint32_t si, float* vals, uint32_t* hist,
       }
     }
     block_minmax<NT>(a, b, reinterpret_cast<float*>(sh));
-    a = a + 0.0f;
-    b = b + 0.0f;
-    mn = a;
-    scale = (b == a) ? 0.0f : (b - a) / P.levels;
+    codec_range(a, b, P.levels, mn, scale);
   }
   STAMP(P, s, 6);
   if (t == 0) {
@@ -2091,10 +2099,7 @@ DEV void select_finish(const Params& P, uint32_t s, const SegDev& sd, SelSmem& S
       gmx = fmax_nan(gmx, -tv);
     }
     block_minmax<NT>(gmn, gmx, S.shf);
-    gmn = gmn + 0.0f;
-    gmx = gmx + 0.0f;
-    mn = gmn;
-    scale = (gmx == gmn) ? 0.0f : (gmx - gmn) / P.levels;
+    codec_range(gmn, gmx, P.levels, mn, scale);
   }
   if (t == 0) {
     pst(P, P.tstar + s, T);
@@ -2789,6 +2794,78 @@ DEV uint32_t dense_code(float x, float mn, float scale, float y, float levels) {
   return (uint32_t)(uint8_t)(rt < levels ? rt : levels);
 }
 
+// ... and that choice, made once per wave: f(qz) runs with qz(x) = dense_code<RCP> of the range, RCP a compile-time
+// value inside f (two copies of f's straight-line loop behind one wave-uniform branch)
+template <class F>
+DEV void with_rcp(float mn, float scale, float levels, F&& f) {
+  auto run = [&](auto rcp_tag) {
+    constexpr bool RCP = decltype(rcp_tag)::value;
+    const float y = RCP ? 1.0f / scale : 0.0f;
+    f([&](float x) -> uint32_t { return dense_code<RCP>(x, mn, scale, y, levels); });
+  };
+  if (dense_rcp_scale(scale))  // (scale 0, NaN, inf or extreme: the division)
+    run(std::true_type{});
+  else
+    run(std::false_type{});
+}
+
+// the NaN-ignoring min / max of a loaded unit over the whole wave (every lane gets both)
+DEV void dense_unit_minmax(const float4 (&v)[UNIT_IT], uint32_t len, uint32_t lane, float& a, float& b) {
+  a = qnan(), b = qnan();
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    const uint32_t e0 = (it * 64 + lane) * 4;
+    const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x = (len == UNIT || e0 + j < len) ? xs[j] : qnan();  // (loads past len read 0)
+      a = fmin_nan(a, x);
+      b = fmax_nan(b, x);
+    }
+  }
+  a = wave_min(a);
+  b = wave_max(b);
+}
+
+// A dense unit's codes sit at the positions themselves (k == n: entry e is element e): its first entry in vals, and
+// whether its codes can move as whole dwords — they start 4-byte aligned (16-byte for raw floats) and end on a dword.
+// The one copy: every kernel that reads or writes a unit's codes takes the same branch.
+DEV uint64_t dense_unit_entry(const UnitDev& U) { return U.out_off + U.start; }
+DEV bool dense_unit_vec(const UnitDev& U) {
+  const uint64_t o = dense_unit_entry(U);
+  return (o & 3u) == 0 && (U.len & 3u) == 0;
+}
+
+// Four codes of a unit at byte offset boff of the resource over its `len` codes (bytes_rsrc): one dword where the
+// unit's codes are whole dwords (vec), else four range-checked bytes — a load past len gives 0, a store there is dropped.
+DEV uint32_t dense_codes_row(__amdgpu_buffer_rsrc_t r, bool vec, uint32_t boff) {
+  if (vec) return __builtin_amdgcn_raw_buffer_load_b32(r, (int)boff, 0, 0);
+  return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)boff, 0, 0) |
+         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)boff + 1, 0, 0) << 8) |
+         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)boff + 2, 0, 0) << 16) |
+         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)boff + 3, 0, 0) << 24);
+}
+
+DEV void dense_codes_store_row(__amdgpu_buffer_rsrc_t r, bool vec, uint32_t boff, const uint32_t (&c)[4]) {
+  if (vec) {
+    __builtin_amdgcn_raw_buffer_store_b32(c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), r, (int)boff, 0, 0);
+  } else {
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)c[j], r, (int)(boff + j), 0, 0);
+  }
+}
+
+// The end of every dense decoder, one row (lane l's float4 of row `row`) at a time: base + x, and the store — 16 bytes
+// where the unit's length is a multiple of four, else four dwords, the range check dropping those past the end.
+DEV float4 dense_add_base(float4 b, float4 x) { return make_float4(b.x + x.x, b.y + x.y, b.z + x.z, b.w + x.w); }
+template <int AUX = STORE_AUX>
+DEV void dense_store_row(__amdgpu_buffer_rsrc_t rout, uint32_t len, uint32_t row, uint32_t lane, float4 x) {
+  if ((len & 3u) == 0)
+    unit_store_x4<AUX>(rout, (row * 64 + lane) * 16, x);
+  else
+    unit_store_x1x4<AUX>(rout, (row * 64 + lane) * 16, x);
+}
+
 template <bool DELTA, bool XCD>
 __global__ __launch_bounds__(BLOCK) void k_dense_minmax(Params P) {
   const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
@@ -2797,20 +2874,8 @@ __global__ __launch_bounds__(BLOCK) void k_dense_minmax(Params P) {
   float4 v[UNIT_IT];
   dense_unit_load<DELTA, DENSE_MM_AUX>(P, U, v);
   const uint32_t lane = lane_id();
-  float a = qnan(), b = qnan();
-#pragma unroll
-  for (uint32_t it = 0; it < UNIT_IT; ++it) {
-    const uint32_t e0 = (it * 64 + lane) * 4;
-    const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x = (U.len == UNIT || e0 + j < U.len) ? xs[j] : qnan();  // (loads past len read 0)
-      a = fmin_nan(a, x);
-      b = fmax_nan(b, x);
-    }
-  }
-  a = wave_min(a);
-  b = wave_max(b);
+  float a, b;
+  dense_unit_minmax(v, U.len, lane, a, b);
   if (lane == 0) {
     P.umm[2 * u] = a;
     P.umm[2 * u + 1] = b;
@@ -2833,12 +2898,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_seg(Params P) {
   block_minmax<BLOCK>(a, b, shf);
   if (threadIdx.x == 0) {
     float mn = 0.0f, scale = 0.0f;
-    if (!RAW && sd.n != 0) {
-      a = a + 0.0f;
-      b = b + 0.0f;
-      mn = a;
-      scale = (b == a) ? 0.0f : (b - a) / P.levels;
-    }
+    if (!RAW && sd.n != 0) codec_range(a, b, P.levels, mn, scale);
     P.mn[s] = mn;
     P.scale[s] = scale;
   }
@@ -2885,10 +2945,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
         a = fmin_nan(a, t.x);
         b = fmax_nan(b, t.y);
       }
-      a = wave_min(a) + 0.0f;
-      b = wave_max(b) + 0.0f;
-      mn = a;
-      scale = (b == a) ? 0.0f : (b - a) / P.levels;
+      codec_range(wave_min(a), wave_max(b), P.levels, mn, scale);
     }
     if (u == sd.unit_begin && lane == 0) {
       P.mn[U.seg] = mn;
@@ -2898,12 +2955,10 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
     mn = P.mn[U.seg];
     scale = P.scale[U.seg];
   }
-  const uint64_t o = U.out_off + U.start;  // the unit's first entry (k == n: entry e is element e)
-  // whole-dword stores when the unit's codes start 4-byte aligned (16-byte for raw floats) and end on a dword
-  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;
+  const uint64_t o = dense_unit_entry(U);
+  const bool vec = dense_unit_vec(U);
   if (RAW) {
-    float* dst = static_cast<float*>(P.vals) + o;
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(dst, (short)0, (int)(U.len * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r = unit_rsrc(static_cast<float*>(P.vals) + o, U.len);
 #pragma unroll
     for (uint32_t it = 0; it < UNIT_IT; ++it) {
       if (vec)
@@ -2912,32 +2967,16 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
         unit_store_x1x4<0>(r, (it * 64 + lane) * 16, v[it]);
     }
   } else {
-    uint8_t* dst = static_cast<uint8_t*>(P.vals) + o;
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(dst, (short)0, (int)U.len, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r = bytes_rsrc(static_cast<uint8_t*>(P.vals) + o, U.len);
     // dense_code's reciprocal form: the IEEE division sequence it replaces cost 3.5 us of the download step
     // (profiles/r06_ab_dense_segred.txt)
-    auto codes = [&](auto rcp_tag) {
-      constexpr bool RCP = decltype(rcp_tag)::value;
-      const float y = RCP ? 1.0f / scale : 0.0f;
-      auto qz = [&](float x) -> uint32_t { return dense_code<RCP>(x, mn, scale, y, P.levels); };
+    with_rcp(mn, scale, P.levels, [&](auto qz) {
 #pragma unroll
       for (uint32_t it = 0; it < UNIT_IT; ++it) {
-        const uint32_t q0 = qz(v[it].x), q1 = qz(v[it].y), q2 = qz(v[it].z), q3 = qz(v[it].w);
-        const uint32_t boff = (it * 64 + lane) * 4;
-        if (vec) {
-          __builtin_amdgcn_raw_buffer_store_b32(q0 | (q1 << 8) | (q2 << 16) | (q3 << 24), r, (int)boff, 0, 0);
-        } else {  // (range-checked per byte: the unit's tail past len is dropped)
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q0, r, (int)boff, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q1, r, (int)boff + 1, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q2, r, (int)boff + 2, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q3, r, (int)boff + 3, 0, 0);
-        }
+        const uint32_t c[4] = {qz(v[it].x), qz(v[it].y), qz(v[it].z), qz(v[it].w)};
+        dense_codes_store_row(r, vec, (it * 64 + lane) * 4, c);
       }
-    };
-    if (dense_rcp_scale(scale))  // (uniform per wave; scale 0, NaN, inf or extreme: the division)
-      codes(std::true_type{});
-    else
-      codes(std::false_type{});
+    });
   }
   if (P.idx != nullptr) {  // a caller that asked for the (implied) indices
     for (uint32_t e = lane; e < U.len; e += 64) P.idx[o + e] = (int32_t)(U.start + e);
@@ -2945,22 +2984,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
   if (P.ustart_out != nullptr && lane == 0) P.ustart_out[u] = U.start;
 }
 
-// a dense plan's uint8 codes, one row of a unit at a time (shared by k_dense_deq and k_aggregate_dense): the resource over
-// the unit's `len` codes at src (loads past them return 0), lane l's four codes of row `row` as one dword — a dword load
-// where the unit's codes start and end on one (vec), else four byte loads — and their decoded values
-DEV __amdgpu_buffer_rsrc_t dense_codes_rsrc(const uint8_t* src, uint32_t len) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), (short)0, (int)len, 0x00020000);
-}
-
-DEV uint32_t dense_codes_row(__amdgpu_buffer_rsrc_t r, bool vec, uint32_t row, uint32_t lane) {
-  const uint32_t b = (row * 64 + lane) * 4;
-  if (vec) return __builtin_amdgcn_raw_buffer_load_b32(r, (int)b, 0, 0);
-  return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b, 0, 0) |
-         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 1, 0, 0) << 8) |
-         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 2, 0, 0) << 16) |
-         ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)b + 3, 0, 0) << 24);
-}
-
+// the decoded values of four uint8 codes in one dword (dense_codes_row)
 DEV float4 dense_codes_values(uint32_t w, float mn, float scale) {
   return make_float4(dequantize((uint8_t)(w & 0xFFu), mn, scale), dequantize((uint8_t)((w >> 8) & 0xFFu), mn, scale),
                      dequantize((uint8_t)((w >> 16) & 0xFFu), mn, scale), dequantize((uint8_t)(w >> 24), mn, scale));
@@ -2970,8 +2994,8 @@ DEV float4 dense_codes_values(uint32_t w, float mn, float scale) {
 // in d[it]; positions past the unit's end hold mn (code 0) or 0.0f (raw) and are never stored
 template <bool RAW>
 DEV void dense_unit_values(const Params& P, const UnitDev& U, float mn, float scale, uint32_t lane, float4 (&d)[UNIT_IT]) {
-  const uint64_t o = U.out_off + U.start;
-  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;
+  const uint64_t o = dense_unit_entry(U);
+  const bool vec = dense_unit_vec(U);
   if (RAW) {
     const float* src = static_cast<const float*>(P.cvals) + o;
     const __amdgpu_buffer_rsrc_t r = unit_rsrc(src, U.len);
@@ -2988,10 +3012,10 @@ DEV void dense_unit_values(const Params& P, const UnitDev& U, float mn, float sc
       }
     }
   } else {
-    const __amdgpu_buffer_rsrc_t r = dense_codes_rsrc(static_cast<const uint8_t*>(P.cvals) + o, U.len);
+    const __amdgpu_buffer_rsrc_t r = bytes_rsrc(static_cast<const uint8_t*>(P.cvals) + o, U.len);
     uint32_t w[UNIT_IT];
 #pragma unroll
-    for (uint32_t it = 0; it < UNIT_IT; ++it) w[it] = dense_codes_row(r, vec, it, lane);
+    for (uint32_t it = 0; it < UNIT_IT; ++it) w[it] = dense_codes_row(r, vec, (it * 64 + lane) * 4);
 #pragma unroll
     for (uint32_t it = 0; it < UNIT_IT; ++it) d[it] = dense_codes_values(w[it], mn, scale);
   }
@@ -3011,14 +3035,8 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq(Params P) {
 #pragma unroll
   for (uint32_t it = 0; it < UNIT_IT; ++it) {
     float4 x = d[it];
-    if (HASBASE) {
-      const float4 b = unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16);
-      x = make_float4(b.x + x.x, b.y + x.y, b.z + x.z, b.w + x.w);
-    }
-    if ((U.len & 3u) == 0)
-      unit_store_x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
-    else
-      unit_store_x1x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
+    if (HASBASE) x = dense_add_base(unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16), x);
+    dense_store_row(rout, U.len, it, lane, x);
   }
 }
 
@@ -3058,12 +3076,8 @@ __global__ __launch_bounds__(BLOCK) void k_ef_accumulate(Params P) {
     }
 #pragma unroll
     for (uint32_t it = 0; it < EF_ROWS; ++it) {
-      const uint32_t b = ((i0 + it) * 64 + lane) * 16;
       const float4 a = make_float4(d[it].x + r[it].x, d[it].y + r[it].y, d[it].z + r[it].z, d[it].w + r[it].w);
-      if ((len & 3u) == 0)
-        unit_store_x4<EF_STORE_AUX>(rr, b, a);
-      else
-        unit_store_x1x4<EF_STORE_AUX>(rr, b, a);
+      dense_store_row<EF_STORE_AUX>(rr, len, i0 + it, lane, a);
     }
   }
 }
@@ -3123,14 +3137,10 @@ __global__ __launch_bounds__(BLOCK) void k_ef_commit_dense(Params P) {
   const __amdgpu_buffer_rsrc_t rr = unit_rsrc(P.out + U.off, U.len);
 #pragma unroll
   for (uint32_t it = 0; it < UNIT_IT; ++it) {
-    const uint32_t b = (it * 64 + lane) * 16;
-    const float4 a = unit_load_x4<false>(rr, rr, b);
+    const float4 a = unit_load_x4<false>(rr, rr, (it * 64 + lane) * 16);
     const float4 v = make_float4(ef_residual(a.x, d[it].x), ef_residual(a.y, d[it].y), ef_residual(a.z, d[it].z),
                                  ef_residual(a.w, d[it].w));
-    if ((U.len & 3u) == 0)
-      unit_store_x4<EF_STORE_AUX>(rr, b, v);
-    else
-      unit_store_x1x4<EF_STORE_AUX>(rr, b, v);
+    dense_store_row<EF_STORE_AUX>(rr, U.len, it, lane, v);
   }
 }
 
@@ -3143,6 +3153,25 @@ __global__ __launch_bounds__(BLOCK) void k_ef_commit_dense(Params P) {
 //   k_unpack  one wave per unit of the plan's table, its entry range from the starts (clamped as k_decode_lds clamps)
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t PACK_E = 32;  // entries per k_pack lane: 32 fields of w bits are exactly w words
+
+// N fields of W bits each as the N W / 32 whole words of a little-endian bit stream (k_pack, k_pack_dense). Fully
+// unrolled: nb and wi are compile-time values, f[] and word[] stay in registers.
+template <uint32_t W, uint32_t N>
+DEV void pack_fields(const uint32_t (&f)[N], uint32_t (&word)[W * N / 32u]) {
+  static_assert(W * N % 32u == 0, "whole words");
+  uint64_t acc = 0;
+  uint32_t nb = 0, wi = 0;
+#pragma unroll
+  for (uint32_t i = 0; i < N; ++i) {
+    acc |= (uint64_t)f[i] << nb;
+    nb += W;
+    if (nb >= 32u) {
+      word[wi++] = (uint32_t)acc;
+      acc >>= 32;
+      nb -= 32u;
+    }
+  }
+}
 
 // B: code bits (0 = none: a raw plan's values are not read). idx and vals are 16-byte aligned (checked by the entry
 // point), so a full lane reads its 32 indices as eight b128 loads and its 32 codes as two.
@@ -3186,18 +3215,7 @@ __global__ __launch_bounds__(BLOCK) void k_pack(const int32_t* __restrict__ idx,
     }
   }
   uint32_t word[W];
-  uint64_t acc = 0;
-  uint32_t nb = 0, wi = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < PACK_E; ++i) {  // (fully unrolled: nb and wi are compile-time values)
-    acc |= (uint64_t)f[i] << nb;
-    nb += W;
-    if (nb >= 32u) {
-      word[wi++] = (uint32_t)acc;
-      acc >>= 32;
-      nb -= 32u;
-    }
-  }
+  pack_fields<W, PACK_E>(f, word);
   const uint32_t nw = (cnt * W + 31u) >> 5;  // words this lane owns (W for a full lane); every one written once
   uint32_t* o = out + t * W;
 #pragma unroll
@@ -3243,22 +3261,32 @@ __global__ __launch_bounds__(BLOCK) void k_unpack(Params P, const uint32_t* __re
 // One wave per unit owns whole words: plain stores, no atomics.
 //   k_pack_dense     a lane takes 32-entry groups (two per unit): 32 codes -> B words
 //   k_unpack_dense   the inverse: B words -> 32 codes, written inside vals[out_off_s + [0, n_s)) only
-//   k_dense_deq_packed  k_dense_deq reading the stream itself: a lane's four elements of a row are 4 B bits
+//   k_dense_deq_stream  k_dense_deq reading the stream itself: a lane's four elements of a row are 4 B bits; the
+//                       range of an element its segment's (wire v4) or its unit's (wire v5, below)
+// Shared pieces, one copy each: the unit's words (dense_unit_word_off: every kernel here, k_dense_block_quant,
+// k_aggregate_dense; dense_unit_words_rsrc: the three kernels here), the unit's codes (dense_unit_entry / dense_unit_vec / dense_codes_row /
+// dense_codes_store_row: the dense section's), a row of the stream (dense_row_words / dense_row_values:
+// k_dense_deq_stream, k_aggregate_dense), the field accumulator (pack_fields: k_pack's).
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t DPACK_E = 32;                      // entries per group: B whole words
 constexpr uint32_t DPACK_G = UNIT / DPACK_E / 64;     // groups per lane per unit (2)
 
-// the unit's words inside the stream and how many it owns (the segment's last unit: up to the segment's last word)
-// (dense_unit_word_off: where they start, for a caller with one stream per client)
+// where the unit's words start inside the stream and how many it owns (the segment's last unit: up to the segment's
+// last word)
 template <uint32_t B>
 DEV uint64_t dense_unit_word_off(const uint64_t* pw, const UnitDev& U, uint32_t& nwords) {
   nwords = ((uint32_t)U.len * B + 31u) >> 5;
   return pw[U.seg] + (uint64_t)(UNIT / 32u * B) * (U.start >> UNIT_SHIFT);
 }
 
+// the resource over the unit's words: a load past them returns 0, a store there is dropped — never another segment's
+// word or past the stream (they lie inside the segment's W_s). The one copy of the stream's addressing, with
+// dense_row_words / dense_row_values below.
 template <uint32_t B>
-DEV const uint32_t* dense_unit_words(const uint32_t* packed, const uint64_t* pw, const UnitDev& U, uint32_t& nwords) {
-  return packed + dense_unit_word_off<B>(pw, U, nwords);
+DEV __amdgpu_buffer_rsrc_t dense_unit_words_rsrc(const uint32_t* packed, const uint64_t* pw, const UnitDev& U) {
+  uint32_t nwords;
+  const uint64_t woff = dense_unit_word_off<B>(pw, U, nwords);
+  return bytes_rsrc(packed + woff, nwords * 4u);
 }
 
 template <uint32_t B>
@@ -3268,47 +3296,30 @@ __global__ __launch_bounds__(BLOCK) void k_pack_dense(Params P, const uint64_t* 
   if (u >= P.n_units) return;
   const UnitDev U = P.units[u];
   const uint32_t lane = lane_id();
-  const uint64_t o = U.out_off + U.start;  // the unit's first code (k == n: entry e is element e)
-  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;  // (as k_dense_quant: whole dwords, start to end)
+  const bool vec = dense_unit_vec(U);
   // range-checked to the unit's codes: a group's tail past len reads 0, which is the padding
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(vals + o), (short)0, (int)U.len, 0x00020000);
-  uint32_t nwords;
-  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
-  const __amdgpu_buffer_rsrc_t rout =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rin = bytes_rsrc(vals + dense_unit_entry(U), U.len);
+  const __amdgpu_buffer_rsrc_t rout = dense_unit_words_rsrc<B>(packed, pw, U);
   uint32_t q[DPACK_G][DPACK_E / 4];  // four codes per dword
 #pragma unroll
   for (uint32_t g = 0; g < DPACK_G; ++g) {
     const uint32_t b0 = (g * 64 + lane) * DPACK_E;
-    if (vec) {  // (dword loads: the codes' start is 4-byte aligned, no more)
+    // The wave-uniform branch stands outside the loop on purpose: one loop over dense_codes_row(rin, vec, ...) compiles
+    // to a branch per dword (about 100 instructions more per kernel, checked in the gfx950 assembly), not one per group.
+    if (vec) {
 #pragma unroll
-      for (uint32_t i = 0; i < DPACK_E / 4; ++i) q[g][i] = __builtin_amdgcn_raw_buffer_load_b32(rin, (int)(b0 + 4 * i), 0, 0);
+      for (uint32_t i = 0; i < DPACK_E / 4; ++i) q[g][i] = dense_codes_row(rin, true, b0 + 4 * i);
     } else {
 #pragma unroll
-      for (uint32_t i = 0; i < DPACK_E / 4; ++i)
-        q[g][i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i), 0, 0) |
-                  ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i + 1), 0, 0) << 8) |
-                  ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i + 2), 0, 0) << 16) |
-                  ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rin, (int)(b0 + 4 * i + 3), 0, 0) << 24);
+      for (uint32_t i = 0; i < DPACK_E / 4; ++i) q[g][i] = dense_codes_row(rin, false, b0 + 4 * i);
     }
   }
 #pragma unroll
   for (uint32_t g = 0; g < DPACK_G; ++g) {
-    uint32_t word[B];
-    uint64_t acc = 0;
-    uint32_t nb = 0, wi = 0;
+    uint32_t c[DPACK_E], word[B];
 #pragma unroll
-    for (uint32_t i = 0; i < DPACK_E; ++i) {  // (fully unrolled: nb and wi are compile-time values)
-      const uint32_t c = (q[g][i >> 2] >> ((i & 3u) * 8u)) & ((1u << B) - 1u);
-      acc |= (uint64_t)c << nb;
-      nb += B;
-      if (nb >= 32u) {
-        word[wi++] = (uint32_t)acc;
-        acc >>= 32;
-        nb -= 32u;
-      }
-    }
+    for (uint32_t i = 0; i < DPACK_E; ++i) c[i] = (q[g][i >> 2] >> ((i & 3u) * 8u)) & ((1u << B) - 1u);
+    pack_fields<B, DPACK_E>(c, word);
     const uint32_t w0 = (g * 64 + lane) * B;  // words past the unit's own are dropped by the range check
 #pragma unroll
     for (uint32_t i = 0; i < B; ++i) __builtin_amdgcn_raw_buffer_store_b32(word[i], rout, (int)((w0 + i) * 4u), 0, 0);
@@ -3322,14 +3333,10 @@ __global__ __launch_bounds__(BLOCK) void k_unpack_dense(Params P, const uint64_t
   if (u >= P.n_units) return;
   const UnitDev U = P.units[u];
   const uint32_t lane = lane_id();
-  const uint64_t o = U.out_off + U.start;
-  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;
-  uint32_t nwords;
-  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+  const bool vec = dense_unit_vec(U);
+  const __amdgpu_buffer_rsrc_t rin = dense_unit_words_rsrc<B>(packed, pw, U);
   // range-checked to the unit's codes: a store past len is dropped (only vals[out_off + [0, n)) is written)
-  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(vals + o, (short)0, (int)U.len, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rout = bytes_rsrc(vals + dense_unit_entry(U), U.len);
   uint32_t w[DPACK_G][B + 1];
 #pragma unroll
   for (uint32_t g = 0; g < DPACK_G; ++g) {
@@ -3351,28 +3358,14 @@ __global__ __launch_bounds__(BLOCK) void k_unpack_dense(Params P, const uint64_t
         if (sh + B > 32u) v |= w[g][wd + 1] << (32u - sh);
         c[j] = v & ((1u << B) - 1u);
       }
-      if (vec) {
-        __builtin_amdgcn_raw_buffer_store_b32(c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), rout, (int)(b0 + 4 * d), 0, 0);
-      } else {
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j)
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)c[j], rout, (int)(b0 + 4 * d + j), 0, 0);
-      }
+      dense_codes_store_row(rout, vec, b0 + 4 * d, c);
     }
   }
 }
 
-// k_dense_deq with its values read from the dense stream: lane l's four elements of row it are the 4 B bits at bit
-// (it * 64 + l) * 4 B of the unit's words — one word, or two when the field straddles (never for B = 1, 2, 4, 8). The
-// loads are range-checked to the unit's own words, which lie inside its segment's W_s: a field at the end reads 0
-// past them, never another segment's word or past the stream. Same dequantize, base + x and stores as k_dense_deq.
-// (dense_deq_packed_unit: one unit of it, with the range (mn, scale) its caller read — the segment's here, the unit's
-// own in k_dense_block_deq. Its pieces — the resource over a unit's words, a row's words, a row's values — are
-// k_aggregate_dense's loader too: one copy of the stream's addressing.)
-DEV __amdgpu_buffer_rsrc_t dense_words_rsrc(const uint32_t* words, uint32_t nwords) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
-}
-
+// A row of the stream: lane l's four elements of row `row` are the 4 B bits at bit (row * 64 + l) * 4 B of the unit's
+// words — one word, or two when the field straddles (never for B = 1, 2, 4, 8); a field at the unit's end reads 0 past
+// its words (dense_unit_words_rsrc). Shared by k_dense_deq_stream and k_aggregate_dense.
 template <uint32_t B>
 DEV void dense_row_words(__amdgpu_buffer_rsrc_t rin, uint32_t row, uint32_t lane, uint32_t& lo, uint32_t& hi) {
   constexpr bool STRADDLE = (32u % (4u * B)) != 0u;
@@ -3391,13 +3384,27 @@ DEV float4 dense_row_values(uint32_t lo, uint32_t hi, uint32_t row, uint32_t lan
                      dequantize((uint8_t)((f >> (3 * B)) & M), mn, scale));
 }
 
-template <uint32_t B, bool HASBASE>
-DEV void dense_deq_packed_unit(const Params& P, const UnitDev& U, const uint64_t* __restrict__ pw,
-                               const uint32_t* __restrict__ packed, float mn, float scale) {
-  const uint32_t lane = lane_id();
-  uint32_t nwords;
-  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
-  const __amdgpu_buffer_rsrc_t rin = dense_words_rsrc(words, nwords);
+// Which range (mn, scale) decodes an element of a stream: its unit's own (PERUNIT: wire v5, block-wise) or its
+// segment's (wire v4). The one copy of the rule, for k_dense_deq_stream and k_aggregate_dense.
+template <bool PERUNIT>
+DEV uint32_t dense_range_index(uint32_t u, const UnitDev& U) {
+  return PERUNIT ? u : U.seg;
+}
+
+// k_dense_deq with its values read from the dense stream, the ranges at rmn / rscale [dense_range_index]: wire v4's
+// decode (PERUNIT false: one range per segment) and wire v5's (true: one per unit) are this one kernel. Same
+// dequantize, base + x and stores as k_dense_deq.
+template <uint32_t B, bool PERUNIT, bool HASBASE, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_deq_stream(Params P, const uint64_t* __restrict__ pw,
+                                                            const uint32_t* __restrict__ packed,
+                                                            const float* __restrict__ rmn,
+                                                            const float* __restrict__ rscale) {
+  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id(), ri = dense_range_index<PERUNIT>(u, U);
+  const float mn = rmn[ri], scale = rscale[ri];
+  const __amdgpu_buffer_rsrc_t rin = dense_unit_words_rsrc<B>(packed, pw, U);
   uint32_t lo[UNIT_IT], hi[UNIT_IT];
 #pragma unroll
   for (uint32_t it = 0; it < UNIT_IT; ++it) dense_row_words<B>(rin, it, lane, lo[it], hi[it]);
@@ -3406,24 +3413,9 @@ DEV void dense_deq_packed_unit(const Params& P, const UnitDev& U, const uint64_t
 #pragma unroll
   for (uint32_t it = 0; it < UNIT_IT; ++it) {
     float4 x = dense_row_values<B>(lo[it], hi[it], it, lane, mn, scale);
-    if (HASBASE) {
-      const float4 b = unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16);
-      x = make_float4(b.x + x.x, b.y + x.y, b.z + x.z, b.w + x.w);
-    }
-    if ((U.len & 3u) == 0)
-      unit_store_x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
-    else
-      unit_store_x1x4<STORE_AUX>(rout, (it * 64 + lane) * 16, x);
+    if (HASBASE) x = dense_add_base(unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16), x);
+    dense_store_row(rout, U.len, it, lane, x);
   }
-}
-
-template <uint32_t B, bool HASBASE, bool XCD>
-__global__ __launch_bounds__(BLOCK) void k_dense_deq_packed(Params P, const uint64_t* __restrict__ pw,
-                                                            const uint32_t* __restrict__ packed) {
-  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
-  if (u >= P.n_units) return;
-  const UnitDev U = P.units[u];
-  dense_deq_packed_unit<B, HASBASE>(P, U, pw, packed, P.cmn[U.seg], P.cscale[U.seg]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3432,7 +3424,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq_packed(Params P, const uint
 // B-bit stream, in one pass: no min / max pre-pass, no segment reduce, no byte-per-element intermediate.
 //   k_dense_block_quant  one wave per unit: load (16 float4 per lane), the wave's NaN-ignoring min / max -> bmn[u],
 //                        bscale[u], quantise (dense_code: k_dense_quant's arithmetic), emit the unit's words
-//   k_dense_block_deq    k_dense_deq_packed with (mn, scale) = (bmn[u], bscale[u])
+//   the decode is k_dense_deq_stream<PERUNIT> with (mn, scale) = (bmn[u], bscale[u])
 // Emission: lane l's four codes of row it are one 4 B-bit field, field f = it * 64 + l at bit 4 B f of the unit's
 // sub-stream. The wave writes its 1024 fields to its own 4 KB of LDS, then lane l builds the words l, l + 64, ... of
 // the unit (128 B of them) from the fields that overlap each — 8 / B fields where 4 B divides 32, at most 1 +
@@ -3455,28 +3447,14 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uin
   uint32_t* fld = sfld[threadIdx.x >> 6];
   float4 v[UNIT_IT];
   dense_unit_load<DELTA, DENSE_Q_AUX>(P, U, v);
-  float a = qnan(), b = qnan();
-#pragma unroll
-  for (uint32_t it = 0; it < UNIT_IT; ++it) {
-    const uint32_t e0 = (it * 64 + lane) * 4;
-    const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x = (len == UNIT || e0 + j < len) ? xs[j] : qnan();  // (as k_dense_minmax: loads past len read 0)
-      a = fmin_nan(a, x);
-      b = fmax_nan(b, x);
-    }
-  }
-  a = wave_min(a) + 0.0f;
-  b = wave_max(b) + 0.0f;
-  const float mn = a, scale = (b == a) ? 0.0f : (b - a) / P.levels;
+  float a, b, mn, scale;
+  dense_unit_minmax(v, len, lane, a, b);
+  codec_range(a, b, P.levels, mn, scale);
   if (lane == 0) {
     bmn[u] = mn;
     bscale[u] = scale;
   }
-  auto fields = [&](auto rcp_tag) {
-    constexpr bool RCP = decltype(rcp_tag)::value;
-    const float y = RCP ? 1.0f / scale : 0.0f;
+  with_rcp(mn, scale, P.levels, [&](auto qz) {
 #pragma unroll
     for (uint32_t it = 0; it < UNIT_IT; ++it) {
       const uint32_t e0 = (it * 64 + lane) * 4;
@@ -3484,21 +3462,18 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uin
       uint32_t f = 0;
 #pragma unroll
       for (uint32_t j = 0; j < 4; ++j) {
-        const uint32_t q = dense_code<RCP>(xs[j], mn, scale, y, P.levels);
+        const uint32_t q = qz(xs[j]);
         f |= ((len == UNIT || e0 + j < len) ? q : 0u) << (j * B);  // (a code past len is 0: the padding)
       }
       fld[it * 64 + lane] = f;
     }
-  };
-  if (dense_rcp_scale(scale))  // (uniform per wave, as k_dense_quant)
-    fields(std::true_type{});
-  else
-    fields(std::false_type{});
+  });
   lds_order();
+  // (the offset and the resource apart, as k_aggregate_dense: through dense_unit_words_rsrc this kernel compiles to
+  // another register allocation, which measured 2-3 % slower at B = 4)
   uint32_t nwords;
-  const uint32_t* words = dense_unit_words<B>(packed, pw, U, nwords);
-  const __amdgpu_buffer_rsrc_t rout =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(words), (short)0, (int)(nwords * 4u), 0x00020000);
+  const uint64_t woff = dense_unit_word_off<B>(pw, U, nwords);
+  const __amdgpu_buffer_rsrc_t rout = bytes_rsrc(packed + woff, nwords * 4u);
 #pragma unroll
   for (uint32_t i = 0; i < UNIT / 32u * B / 64u; ++i) {
     const uint32_t w = i * 64 + lane, bit = w * 32u;
@@ -3513,17 +3488,6 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uin
     }
     __builtin_amdgcn_raw_buffer_store_b32((uint32_t)acc, rout, (int)(w * 4u), 0, 0);  // (past the unit's words: dropped)
   }
-}
-
-template <uint32_t B, bool HASBASE, bool XCD>
-__global__ __launch_bounds__(BLOCK) void k_dense_block_deq(Params P, const uint64_t* __restrict__ pw,
-                                                           const uint32_t* __restrict__ packed,
-                                                           const float* __restrict__ bmn,
-                                                           const float* __restrict__ bscale) {
-  const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
-  if (u >= P.n_units) return;
-  const UnitDev U = P.units[u];
-  dense_deq_packed_unit<B, HASBASE>(P, U, pw, packed, bmn[u], bscale[u]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3568,11 +3532,11 @@ __global__ __launch_bounds__(BLOCK) void k_aggregate_dense(Params P, const uint6
   const UnitDev U = P.units[u];
   if (r0 * 256u >= U.len) return;
   static_assert(HE == RI * 256u, "rows per wave");
-  const uint32_t ri = KIND == COALAC_AGGD_BLOCK ? u : U.seg;  // the element's range: its unit's or its segment's
+  const uint32_t ri = dense_range_index<KIND == COALAC_AGGD_BLOCK>(u, U);
   const bool avg = A.avg_mask == nullptr || A.avg_mask[U.seg] != 0;
   const uint32_t ncl = avg ? A.clients : 1u;
-  const uint64_t o = U.out_off + U.start;  // CODES: the unit's first code (k == n: entry e is element e)
-  const bool vec = (o & 3u) == 0 && (U.len & 3u) == 0;
+  const uint64_t o = dense_unit_entry(U);  // (CODES)
+  const bool vec = dense_unit_vec(U);
   uint32_t nwords = 0;
   const uint64_t woff = KIND == COALAC_AGGD_CODES ? 0 : dense_unit_word_off<B>(pw, U, nwords);
   const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
@@ -3603,14 +3567,14 @@ __global__ __launch_bounds__(BLOCK) void k_aggregate_dense(Params P, const uint6
 #pragma unroll
     for (uint32_t t = 0; t < D; ++t) {
       if (KIND == COALAC_AGGD_CODES) {
-        const __amdgpu_buffer_rsrc_t rin = dense_codes_rsrc(static_cast<const uint8_t*>(cp[t]) + o, U.len);
+        const __amdgpu_buffer_rsrc_t rin = bytes_rsrc(static_cast<const uint8_t*>(cp[t]) + o, U.len);
 #pragma unroll
         for (uint32_t it = 0; it < RI; ++it) {
-          lo[t][it] = dense_codes_row(rin, vec, r0 + it, lane);
+          lo[t][it] = dense_codes_row(rin, vec, ((r0 + it) * 64 + lane) * 4);
           hi[t][it] = 0u;
         }
-      } else {
-        const __amdgpu_buffer_rsrc_t rin = dense_words_rsrc(static_cast<const uint32_t*>(cp[t]) + woff, nwords);
+      } else {  // (dense_unit_words_rsrc, the unit's offset shared by the clients' streams)
+        const __amdgpu_buffer_rsrc_t rin = bytes_rsrc(static_cast<const uint32_t*>(cp[t]) + woff, nwords * 4u);
 #pragma unroll
         for (uint32_t it = 0; it < RI; ++it) dense_row_words<B>(rin, r0 + it, lane, lo[t][it], hi[t][it]);
       }
@@ -3622,7 +3586,7 @@ __global__ __launch_bounds__(BLOCK) void k_aggregate_dense(Params P, const uint6
       for (uint32_t it = 0; it < RI; ++it) {
         float4 x = KIND == COALAC_AGGD_CODES ? dense_codes_values(lo[t][it], mn[t], sc[t])
                                              : dense_row_values<B>(lo[t][it], hi[t][it], r0 + it, lane, mn[t], sc[t]);
-        if (HASBASE) x = make_float4(bv[it].x + x.x, bv[it].y + x.y, bv[it].z + x.z, bv[it].w + x.w);
+        if (HASBASE) x = dense_add_base(bv[it], x);
         const float4 p = make_float4(x.x * w[t], x.y * w[t], x.z * w[t], x.w * w[t]);
         acc[it] = make_float4(acc[it].x + p.x, acc[it].y + p.y, acc[it].z + p.z, acc[it].w + p.w);
       }
@@ -3630,13 +3594,7 @@ __global__ __launch_bounds__(BLOCK) void k_aggregate_dense(Params P, const uint6
   }
   auto store = [&](auto fin) {
 #pragma unroll
-    for (uint32_t it = 0; it < RI; ++it) {
-      const float4 v = fin(acc[it]);
-      if ((U.len & 3u) == 0)
-        unit_store_x4<STORE_AUX>(rout, ((r0 + it) * 64 + lane) * 16, v);
-      else
-        unit_store_x1x4<STORE_AUX>(rout, ((r0 + it) * 64 + lane) * 16, v);
-    }
+    for (uint32_t it = 0; it < RI; ++it) dense_store_row(rout, U.len, r0 + it, lane, fin(acc[it]));
   };
   if (!avg || A.mode == COALAC_AGG_SUM)
     store([&](float4 a) { return a; });
@@ -4047,14 +4005,6 @@ int packed_args(coalac_plan_t plan, const char* who, bool null_arg, uint64_t pac
   return *done ? COALAC_OK : check_device(plan);
 }
 
-template <uint32_t B = 0>
-void launch_pack(uint32_t b, dim3 g, hipStream_t st, const int32_t* idx, const uint8_t* vals, uint32_t* out, uint64_t K) {
-  if (b == B)
-    hipLaunchKernelGGL((k_pack<B>), g, dim3(BLOCK), 0, st, idx, vals, out, K);
-  else if constexpr (B < 8)
-    launch_pack<B + 1>(b, g, st, idx, vals, out, K);
-}
-
 // the dense stream's entry points: their shared checks (*done: nothing to launch), and the code width -> kernel
 int dense_packed_args(coalac_plan_t plan, const char* who, bool null_arg, uint64_t packed_bytes, bool* done) {
   *done = false;
@@ -4069,12 +4019,37 @@ int dense_packed_args(coalac_plan_t plan, const char* who, bool null_arg, uint64
   return *done ? COALAC_OK : check_device(plan);
 }
 
-template <uint32_t B = 1, typename F>
-void with_code_bits(uint32_t b, F&& f) {
+// f(b, t...) with the code width as a std::integral_constant<uint32_t, b>, b in [B, 8] (B = 0: k_pack's raw plans,
+// which carry no code), and one std::bool_constant per flag behind it (with_flags): a launch is one lambda
+template <uint32_t B = 1, typename F, typename... Flags>
+void with_code_bits(uint32_t b, F&& f, Flags... flags) {
   if (b == B)
-    f(std::integral_constant<uint32_t, B>{});
+    with_flags([&](auto... t) { f(std::integral_constant<uint32_t, B>{}, t...); }, flags...);
   else if constexpr (B < 8)
-    with_code_bits<B + 1>(b, f);
+    with_code_bits<B + 1>(b, f, flags...);
+}
+
+// one wave per unit of the plan: kernel(P, args...) on the call's stream
+template <typename K, typename... Args>
+void launch_units(const Params& P, void* stream, K kernel, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(ceil_div(P.n_units, WAVES)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P, args...);
+}
+
+// coalac_decode_packed / coalac_decode_block behind their own checks: k_dense_deq_stream with one range per segment
+// or (per_unit) per unit
+int decode_stream(coalac_plan_t plan, bool per_unit, const void* d_packed, const float* d_mn, const float* d_scale,
+                  const float* d_base, float* d_out, void* stream) {
+  Params P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  with_code_bits(
+      (uint32_t)plan->bits,
+      [&](auto b, auto pu, auto h, auto x) {
+        launch_units(P, stream, k_dense_deq_stream<b.value, pu.value, h.value, x.value>, plan->dense_pw,
+                     static_cast<const uint32_t*>(d_packed), d_mn, d_scale);
+      },
+      per_unit, d_base != nullptr, !plan->decode_latency);
+  return launched();
 }
 
 }  // namespace
@@ -4389,8 +4364,10 @@ int coalac_pack(coalac_plan_t plan, const int32_t* d_idx, const void* d_vals, vo
     return fail(COALAC_EINVAL, "coalac_pack: idx / vals must be 16-byte aligned, packed 4-byte aligned");
   const uint64_t lanes = (plan->total_k + PACK_E - 1) / PACK_E, blocks = (lanes + BLOCK - 1) / BLOCK;
   if (blocks > 0x7FFFFFFFull) return fail(COALAC_EINVAL, "coalac_pack: plan too large");
-  launch_pack(packed_field_bits(plan) - 12u, dim3((uint32_t)blocks), static_cast<hipStream_t>(stream), d_idx,
-              static_cast<const uint8_t*>(d_vals), static_cast<uint32_t*>(d_packed), plan->total_k);
+  with_code_bits<0>(packed_field_bits(plan) - 12u, [&](auto b) {
+    hipLaunchKernelGGL((k_pack<b.value>), dim3((uint32_t)blocks), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), d_idx,
+                       static_cast<const uint8_t*>(d_vals), static_cast<uint32_t*>(d_packed), plan->total_k);
+  });
   return launched();
 }
 
@@ -4430,11 +4407,9 @@ int coalac_pack_dense(coalac_plan_t plan, const void* d_vals, void* d_packed, ui
   int rc = dense_packed_args(plan, "coalac_pack_dense", !d_vals || !d_packed, packed_bytes, &done);
   if (rc || done) return rc;
   if (addr_bits(d_packed, d_vals) & 3) return fail(COALAC_EINVAL, "coalac_pack_dense: vals / packed must be 4-byte aligned");
-  const Params P = plan->proto;
-  const dim3 g(ceil_div(P.n_units, WAVES));
   with_code_bits((uint32_t)plan->bits, [&](auto b) {
-    hipLaunchKernelGGL((k_pack_dense<b.value>), g, dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P, plan->dense_pw,
-                       static_cast<const uint8_t*>(d_vals), static_cast<uint32_t*>(d_packed));
+    launch_units(plan->proto, stream, k_pack_dense<b.value>, plan->dense_pw, static_cast<const uint8_t*>(d_vals),
+                 static_cast<uint32_t*>(d_packed));
   });
   return launched();
 }
@@ -4444,11 +4419,9 @@ int coalac_unpack_dense(coalac_plan_t plan, const void* d_packed, uint64_t packe
   int rc = dense_packed_args(plan, "coalac_unpack_dense", !d_packed || !d_vals, packed_bytes, &done);
   if (rc || done) return rc;
   if (addr_bits(d_packed, d_vals) & 3) return fail(COALAC_EINVAL, "coalac_unpack_dense: packed / vals must be 4-byte aligned");
-  const Params P = plan->proto;
-  const dim3 g(ceil_div(P.n_units, WAVES));
   with_code_bits((uint32_t)plan->bits, [&](auto b) {
-    hipLaunchKernelGGL((k_unpack_dense<b.value>), g, dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P, plan->dense_pw,
-                       static_cast<const uint32_t*>(d_packed), static_cast<uint8_t*>(d_vals));
+    launch_units(plan->proto, stream, k_unpack_dense<b.value>, plan->dense_pw, static_cast<const uint32_t*>(d_packed),
+                 static_cast<uint8_t*>(d_vals));
   });
   return launched();
 }
@@ -4460,21 +4433,7 @@ int coalac_decode_packed(coalac_plan_t plan, const void* d_packed, uint64_t pack
   if (rc || done) return rc;
   if (addr_bits(d_packed) & 3) return fail(COALAC_EINVAL, "coalac_decode_packed: packed must be 4-byte aligned");
   if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_decode_packed: output/base must be 16-byte aligned");
-  Params P = plan->proto;
-  set_payload(P, nullptr, nullptr, d_mn, d_scale);
-  P.base = d_base;
-  P.out = d_out;
-  const dim3 g(ceil_div(P.n_units, WAVES));
-  const uint32_t* packed = static_cast<const uint32_t*>(d_packed);
-  with_code_bits((uint32_t)plan->bits, [&](auto b) {
-    with_flags(
-        [&](auto h, auto x) {
-          hipLaunchKernelGGL((k_dense_deq_packed<b.value, h.value, x.value>), g, dim3(BLOCK), 0,
-                             static_cast<hipStream_t>(stream), P, plan->dense_pw, packed);
-        },
-        d_base != nullptr, !plan->decode_latency);
-  });
-  return launched();
+  return decode_stream(plan, false, d_packed, d_mn, d_scale, d_base, d_out, stream);
 }
 
 int coalac_encode_block(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
@@ -4492,16 +4451,13 @@ int coalac_encode_block(coalac_plan_t plan, const float* d_in, const float* cons
   P.in = d_in;
   P.inptr = d_seg_in;
   P.base = d_base;
-  const dim3 g(ceil_div(P.n_units, WAVES));
-  with_code_bits((uint32_t)plan->bits, [&](auto b) {
-    with_flags(
-        [&](auto delta, auto x) {
-          hipLaunchKernelGGL((k_dense_block_quant<delta.value, b.value, x.value>), g, dim3(BLOCK), 0,
-                             static_cast<hipStream_t>(stream), P, plan->dense_pw, d_bmn, d_bscale,
-                             static_cast<uint32_t*>(d_packed));
-        },
-        d_base != nullptr, !plan->decode_latency);
-  });
+  with_code_bits(
+      (uint32_t)plan->bits,
+      [&](auto b, auto delta, auto x) {
+        launch_units(P, stream, k_dense_block_quant<delta.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
+                     static_cast<uint32_t*>(d_packed));
+      },
+      d_base != nullptr, !plan->decode_latency);
   return launched();
 }
 
@@ -4513,20 +4469,7 @@ int coalac_decode_block(coalac_plan_t plan, const void* d_packed, uint64_t packe
   if (addr_bits(d_packed, d_bmn, d_bscale) & 3)
     return fail(COALAC_EINVAL, "coalac_decode_block: packed / bmn / bscale must be 4-byte aligned");
   if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_decode_block: output/base must be 16-byte aligned");
-  Params P = plan->proto;
-  P.base = d_base;
-  P.out = d_out;
-  const dim3 g(ceil_div(P.n_units, WAVES));
-  const uint32_t* packed = static_cast<const uint32_t*>(d_packed);
-  with_code_bits((uint32_t)plan->bits, [&](auto b) {
-    with_flags(
-        [&](auto h, auto x) {
-          hipLaunchKernelGGL((k_dense_block_deq<b.value, h.value, x.value>), g, dim3(BLOCK), 0,
-                             static_cast<hipStream_t>(stream), P, plan->dense_pw, packed, d_bmn, d_bscale);
-        },
-        d_base != nullptr, !plan->decode_latency);
-  });
-  return launched();
+  return decode_stream(plan, true, d_packed, d_bmn, d_bscale, d_base, d_out, stream);
 }
 
 int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, const void* d_vals,
@@ -4641,22 +4584,25 @@ int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void
   A.inv_total = 1.0f / total;
   const dim3 g(ceil_div(P.n_units * (uint32_t)AGD_SPLIT, WAVES));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  with_flags(
-      [&](auto hb) {
-        if (kind == COALAC_AGGD_CODES) {
-          hipLaunchKernelGGL((k_aggregate_dense<8, COALAC_AGGD_CODES, hb.value>), g, dim3(BLOCK), 0, st, P, plan->dense_pw, A);
-          return;
-        }
-        with_code_bits((uint32_t)plan->bits, [&](auto b) {
-          if (kind == COALAC_AGGD_PACKED)
-            hipLaunchKernelGGL((k_aggregate_dense<b.value, COALAC_AGGD_PACKED, hb.value>), g, dim3(BLOCK), 0, st, P,
-                               plan->dense_pw, A);
-          else
-            hipLaunchKernelGGL((k_aggregate_dense<b.value, COALAC_AGGD_BLOCK, hb.value>), g, dim3(BLOCK), 0, st, P,
-                               plan->dense_pw, A);
-        });
-      },
-      d_base != nullptr);
+  // One with_code_bits for the three kinds. CODES ignores the width it is handed: its codes are whole bytes, so all
+  // eight arms launch the same <8, CODES, hb>, and it relies on bits being in [1, 8] here (32 was rejected above) —
+  // a width outside that range would launch nothing.
+  auto launch = [&](auto k) {
+    with_code_bits(
+        (uint32_t)plan->bits,
+        [&](auto b, auto hb) {
+          constexpr int KIND = decltype(k)::value;
+          constexpr uint32_t B = KIND == COALAC_AGGD_CODES ? 8u : decltype(b)::value;  // (CODES: whole bytes at any width)
+          hipLaunchKernelGGL((k_aggregate_dense<B, KIND, hb.value>), g, dim3(BLOCK), 0, st, P, plan->dense_pw, A);
+        },
+        d_base != nullptr);
+  };
+  if (kind == COALAC_AGGD_CODES)
+    launch(std::integral_constant<int, COALAC_AGGD_CODES>{});
+  else if (kind == COALAC_AGGD_PACKED)
+    launch(std::integral_constant<int, COALAC_AGGD_PACKED>{});
+  else
+    launch(std::integral_constant<int, COALAC_AGGD_BLOCK>{});
   return launched();
 }
 

@@ -1,4 +1,4 @@
-"""The block-wise dense kernels (k_dense_block_quant / k_dense_block_deq) against the split-table model
+"""The block-wise dense kernels (k_dense_block_quant / k_dense_deq_stream) against the split-table model
 (tests/blockwise_model.py): the existing oracle run over a segment table in which every segment has been cut into its
 4096-element blocks, the stream in wire v4's layout. Every comparison is bit-exact (a NaN range compares as NaN: its
 payload is not part of the spec). Shapes as tests/test_gpu_dense_pack.py: one instantiation per code width, full and

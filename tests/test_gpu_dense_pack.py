@@ -1,4 +1,4 @@
-"""The bit-packed dense codes' kernels (k_pack_dense / k_unpack_dense / k_dense_deq_packed) against the
+"""The bit-packed dense codes' kernels (k_pack_dense / k_unpack_dense / k_dense_deq_stream) against the
 host model of the format, wire.pack_dense_codes / wire.unpack_dense_codes, and against the plain dense decode. Every
 comparison is bit-exact. Small plans: the kernels have one instantiation per code width, a dword and a byte path
 (segments that start at an odd out_off, or whose length is no multiple of 4), full and partial units, and segments

@@ -6,7 +6,7 @@ after a warm-up of every shape), per code width in --bits:
 
   k_pack_dense / k_unpack_dense   each kernel alone, with its algorithmic bytes (the uint8 codes on one side, the
                       stream on the other) against the 8 TB/s HBM peak
-  decode_packed       the dense decode reading the stream (k_dense_deq_packed), and unpack_dense followed by the
+  decode_packed       the dense decode reading the stream (k_dense_deq_stream), and unpack_dense followed by the
                       plain decode, which writes and re-reads one byte per element in between
   encode / decode     the plain dense encode and decode; with --parent-lib (a build of the parent commit's
                       coalac.hip) also those of that library, called through its C ABI directly on the same buffers
