@@ -263,7 +263,12 @@ int coalac_decode_ev(coalac_plan_t plan, const int32_t* d_idx, const void* d_val
  * average the parameters only and keep models[0]'s buffers (coala/server/strategies.py:32-54, 93-124).
  * d_weights: DEVICE fp32[clients] = float(w_i); total: float(sum of the weights). d_out / d_base are
  * indexed like client 0's segments. d_ustart: the clients' per-unit starts, concatenated in client order
- * (uint32[n_units]; required). Events (the _ev variant): [0] at the start, [1] before k_aggregate, [2] after. */
+ * (uint32[n_units]; required). Only the elements of client 0's segments are written to d_out: the alignment pads
+ * between segments and anything after the last segment are left as they are, so a d_out that ends with the last
+ * segment suffices. The encoded arrays may come from untrusted blobs: out-of-range or unsorted indices, or wrong
+ * starts, can mis-aggregate but never write outside the unit — every unit's entry range is clamped and every entry
+ * bounds-checked exactly as coalac_decode does, so the result is still decode-each followed by the weighted sum.
+ * Events (the _ev variant): [0] at the start, [1] before k_aggregate, [2] after. */
 enum { COALAC_AGG_DIV = 0, COALAC_AGG_RECIP = 1, COALAC_AGG_SUM = 2 };
 int coalac_aggregate(coalac_plan_t plan, int clients, const int32_t* d_idx, const void* d_vals,
                      const float* d_mn, const float* d_scale, const uint32_t* d_ustart, const float* d_weights,

@@ -20,6 +20,21 @@ from oracle import codec_oracle as O
 
 pytestmark = pytest.mark.gpu
 
+SENTINEL = 12345.0
+
+
+def sentinel_out(plan):
+    """An output longer than the layout, filled with a sentinel: the kernel writes the segments' elements only."""
+    return torch.full((plan.table.span_per_client + 64,), SENTINEL, dtype=torch.float32, device="cuda")
+
+
+def assert_outside_untouched(plan, g):
+    """Every element of g outside the segments (the alignment pads, the tail) still holds the sentinel."""
+    inside = np.zeros(g.size, bool)
+    for off, n in zip(plan.table.offsets, plan.table.sizes):
+        inside[off:off + n] = True
+    assert np.all(g[~inside] == np.float32(SENTINEL))
+
 
 def setup(layout, ratio, bits, clients, delta, seed=0):
     sizes = fp32_sizes(layout)
@@ -229,13 +244,14 @@ def test_aggregate_many_clients_matches_oracle(cuda, ratio, delta, mode, om):
     h = [t.cpu().numpy() for t in (enc.idx, enc.vals, enc.mn, enc.scale)]
     b = None if base is None else base.cpu().numpy()
     for am in (None, mask):
-        out = plan.aggregate(enc, weights, base=base, mode=mode, avg_mask=am)
+        out = plan.aggregate(enc, weights, base=base, mode=mode, avg_mask=am, out=sentinel_out(plan))
         torch.cuda.synchronize()
         ref = O.aggregate(*h, segs, 8, C, weights, sum(weights), om, base=b, out_span=plan.table.span_per_client,
                           avg_mask=am)
         g = out.cpu().numpy()
         for off, n in zip(plan.table.offsets, plan.table.sizes):
             np.testing.assert_array_equal(g[off:off + n].view(np.uint32), ref[off:off + n].view(np.uint32))
+        assert_outside_untouched(plan, g)
 
 
 @pytest.mark.parametrize("bits", [8, 32])
@@ -265,7 +281,7 @@ def test_aggregate_signed_zero_and_nan_base_matches_oracle(cuda, bits, ratio):
     h = [t.cpu().numpy() for t in (enc.idx, enc.vals, enc.mn, enc.scale)]
     b = base.cpu().numpy()
     for mode, om in (("recip", O.AGG_RECIP), ("sum", O.AGG_SUM)):
-        out = plan.aggregate(enc, weights, base=base, mode=mode)
+        out = plan.aggregate(enc, weights, base=base, mode=mode, out=sentinel_out(plan))
         torch.cuda.synchronize()
         ref = O.aggregate(*h, segs, bits, C, weights, sum(weights), om, base=b, out_span=S)
         g = out.cpu().numpy()
@@ -274,6 +290,7 @@ def test_aggregate_signed_zero_and_nan_base_matches_oracle(cuda, bits, ratio):
             nan = np.isnan(rr)
             np.testing.assert_array_equal(np.isnan(gg), nan)
             np.testing.assert_array_equal(gg[~nan].view(np.uint32), rr[~nan].view(np.uint32))
+        assert_outside_untouched(plan, g)
 
 
 @pytest.mark.parametrize("bits", [8, 32])
@@ -297,13 +314,14 @@ def test_aggregate_more_than_64_clients_matches_oracle(cuda, bits, ratio, delta)
     b = None if base is None else base.cpu().numpy()
     for mode, om, am in (("recip", O.AGG_RECIP, None), ("div", O.AGG_DIV, None),
                          ("sum", O.AGG_SUM, [True, False, True, False])):
-        out = plan.aggregate(enc, weights, base=base, mode=mode, avg_mask=am)
+        out = plan.aggregate(enc, weights, base=base, mode=mode, avg_mask=am, out=sentinel_out(plan))
         torch.cuda.synchronize()
         ref = O.aggregate(*h, segs, bits, C, weights, sum(weights), om, base=b, out_span=plan.table.span_per_client,
                           avg_mask=am)
         g = out.cpu().numpy()
         for off, n in zip(plan.table.offsets, plan.table.sizes):
             np.testing.assert_array_equal(g[off:off + n].view(np.uint32), ref[off:off + n].view(np.uint32))
+        assert_outside_untouched(plan, g)
 
 
 def test_fused_aggregate_recycles_idle_output_modules(cuda):
