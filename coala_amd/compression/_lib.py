@@ -19,6 +19,8 @@ COALAC_AGG_SUM = 2     # acc                    (weighted_sum: the multi-GPU per
 COALAC_AGGD_CODES = 0   # coalac_aggregate_dense reads uint8 codes, one range per segment (wire v2 dense)
 COALAC_AGGD_PACKED = 1  # ... the wire v4 stream, one range per segment
 COALAC_AGGD_BLOCK = 2   # ... the wire v4 stream, one range per 4096-element block (wire v5)
+COALAC_AGGS_ENTRIES = 0  # coalac_aggregate_uploads reads each upload's idx / vals arrays (wire v2)
+COALAC_AGGS_COMPACT = 1  # ... each upload's wire v3 stream
 AGGD_DEPTH = 4          # clients whose code words k_aggregate_dense loads together (AGD_DEPTH in coalac.hip)
 
 ERRORS = {
@@ -71,13 +73,16 @@ SIGNATURES = [
     ("coalac_aggregate_ev", _I, [_P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P, _P]),
     # dense aggregate: plan, clients, kind, codes[], code_bytes, mn[], scale[], weights, total, mode, mask, base, out, stream
     ("coalac_aggregate_dense", _I, [_P, _I, _I, _P, _U64, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
+    # sparse aggregate from the uploads: plan, clients, kind, idx[], packed[], packed_bytes, vals[], mn[], scale[], ustart[],
+    # weights, total, mode, mask, base, out, stream
+    ("coalac_aggregate_uploads", _I, [_P, _I, _I, _P, _P, _U64, _P, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
     ("coalac_gather", _I, [_P, _I, _I, _P, _P]),
     ("coalac_workspace_fallbacks", _I, [_P, _P, _P, ctypes.POINTER(_I)]),
     ("coalac_debug_stamps", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint64), _I]),
     ("coalac_debug_brackets", _I, [_P, _P, _P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _I]),
 ]
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class CodecError(RuntimeError):

@@ -196,7 +196,7 @@ class CompressedUpdate:
         return wire.pack(wh, arrs["mn"], arrs["scale"], arrs.get("idx"), arrs.get("vals"), rawbytes, header_json=hjson,
                          ustart=arrs.get("ustart"), packed=arrs.get("packed"))
 
-    def encoded_to(self, device, staging=None, plan=None):
+    def encoded_to(self, device, staging=None, plan=None, keep_packed=False):
         """The encoded buffers on `device`. An unpickled update (the server side of a remote upload,
         coala/server/service.py:81-111) is moved with ONE host-to-device copy of the blob's mn / scale /
         idx / vals region through `staging` (a pinned host buffer: staging(nbytes) -> uint8 tensor), so
@@ -205,10 +205,29 @@ class CompressedUpdate:
         `plan`.unpack (the decoding plan of this update; without one, the host-unpacked buffers are copied). A
         dense-packed blob (wire v4) for a plan that decodes the stream (decode_packed): its mn ... packed region, the
         stream staying packed on the device; a block-wise blob (wire v5) likewise, always: its decode (decode_block)
-        reads nothing but the stream."""
+        reads nothing but the stream.
+        keep_packed: a compact update stays compact — an Encoded whose `packed` is the entry stream on `device`, idx
+        empty and vals None (bits 32: the fp32 values), for a reader of the stream itself (CodecPlan.aggregate_uploads,
+        kind "compact"); a blob's staged mn ... ustart region is all there is, with no unpack and no room for idx /
+        vals. A carrier that has neither its stream on `device` nor a blob (stream_for), and every other format, is
+        handed out as without the keyword."""
         device = torch.device(device)
         cuda, blob, enc = device.type == "cuda", self._blob[0], self.encoded
         fmt = wire.format_of(self.header)
+        if keep_packed and self.stream_for(device):
+            f32 = self.header["bits"] == RAW_BITS
+            pk = self._packed[0]
+            if pk is not None and pk.device == device and enc.mn.device == device:
+                # a local carrier: its buffers as they are, with the stream the encode packed
+                return Encoded(enc.idx, enc.vals, enc.mn, enc.scale, enc.ustart, pk)
+            no_idx = torch.empty(0, dtype=torch.int32, device=device)
+            if staging is None or not cuda:
+                to = lambda t: t.to(device, non_blocking=True)  # noqa: E731
+                return Encoded(no_idx, to(enc.vals) if f32 else None, to(enc.mn), to(enc.scale), to(enc.ustart),
+                               to(self._blob_stream()))
+            view, _ = self._staged_sections(device, staging)
+            return Encoded(no_idx, view("vals", torch.float32) if f32 else None, view("mn", torch.float32),
+                           view("scale", torch.float32), view("ustart", torch.int32), view("packed", torch.uint32))
         if fmt.stream == "dense" and (fmt.per_block or (cuda and getattr(plan, "decode_packed", None) is not None)):
             # for a plan that reads the stream: an Encoded whose `packed` is the bit-packed stream on `device`, with no
             # uint8 codes there (vals None: CodecPlan.unpack_dense makes them for who needs them); a carrier whose
@@ -237,6 +256,20 @@ class CompressedUpdate:
             plan.unpack(view("packed", torch.uint32), ustart, out=(idx, vals))
             return Encoded(idx, vals, mn, scale, ustart)
         return Encoded(view("idx", torch.int32), view("vals", vdt), mn, scale, ustart)
+
+    def stream_for(self, device):
+        """A compact (wire v3) update whose entry stream a reader on `device` can have without packing anything: the
+        one the encode packed there, or the blob's own section."""
+        if wire.format_of(self.header).stream != "entries" or wire.is_dense(self.header):
+            return False
+        pk = self._packed[0]
+        return self._blob[0] is not None or (pk is not None and pk.device == torch.device(device)
+                                             and self.encoded.mn.device == pk.device)
+
+    def _blob_stream(self):
+        """The blob's packed section as a uint32 tensor (a copy: the blob's bytes are read-only)."""
+        o, n = wire.sections(self._blob[0], self.header)[1]["packed"]
+        return torch.from_numpy(np.frombuffer(self._blob[0], dtype="<u4", count=n // 4, offset=o).copy())
 
     def _staged_sections(self, device, staging, room=0):
         """ONE host-to-device copy of the blob's array sections (they lie back to back: wire.sections) through the pinned
@@ -719,8 +752,42 @@ class UpdateCodec:
         return plan.aggregate_dense(codes, [e.mn for e in encs], [e.scale for e in encs], weights, total=total,
                                     base=base_flat, out=out, mode=mode, avg_mask=avg_mask, kind=kind)
 
+    def sparse_uploads_plan(self, updates, device=None):
+        """The one-layout plan whose aggregate_uploads serves this round (aggregate(..., sparse_uploads=True)), or None
+        where that route does not apply: no fp32 entries, uploads without per-unit starts (wire v1), a dense, dense-
+        packed or block-wise round, a plan whose every segment keeps everything, or a backend whose plans do not
+        offer the method. (Mixed formats are not a uniform round: aggregate() rejects them either way.)"""
+        h0 = updates[0].header
+        fmt = wire.format_of(h0)
+        sizes = _decode_layout(h0["entries"]).sizes
+        if not sizes or wire.is_dense(h0) or fmt.stream == "dense" or not _uniform(updates) or \
+                any(u.encoded.ustart is None for u in updates):
+            return None
+        device = self.backend.default_device() if device is None else torch.device(device)
+        plan = self.plan_for(sizes, device, ratio=h0["ratio"], bits=h0["bits"])
+        return plan if getattr(plan, "aggregate_uploads", None) is not None and not _all_kept(plan) else None
+
+    def _aggregate_uploads(self, plan, updates, weights, total, base_flat, mode, avg_mask, device, out):
+        """aggregate()'s fp32 entries from the uploads' own buffers: every upload on the device in its encoded_to() form
+        (a received blob: ONE pinned copy of its mn ... ustart region, a compact one staying compact; a local carrier
+        where it is), then ONE launch, on the current stream."""
+        cuda = device.type == "cuda"
+        cur = torch.cuda.current_stream(device) if cuda else None
+        # a compact round is read from the streams where every upload has its stream for `device` (stream_for: a
+        # received blob brings it, a local carrier holds the one its encode packed there), else from unpacked entries
+        compact = all(u.stream_for(device) for u in updates)
+        encs = []
+        for u in updates:
+            encs.append(u.encoded_to(device, staging=self._staging if cuda else None, plan=plan, keep_packed=compact))
+            if cuda:
+                self._staged(cur)
+        col = lambda f: [getattr(e, f) for e in encs]  # noqa: E731
+        return plan.aggregate_uploads(col("idx"), col("packed"), col("vals"), col("mn"), col("scale"), col("ustart"),
+                                      weights, total=total, base=base_flat, out=out, mode=mode, avg_mask=avg_mask,
+                                      kind="compact" if compact else "entries")
+
     def aggregate(self, updates, weights, template, base=None, mode="recip", device=None, params_only=False,
-                  dense_kernel=False):
+                  dense_kernel=False, sparse_uploads=False):
         """Fused decode + FedAvg of several CompressedUpdates of one layout -> nn.Module (recycled from the
         decode pool once idle, as decode_module's are: a dropped earlier result is aggregated into).
 
@@ -741,6 +808,11 @@ class UpdateCodec:
         offers it: every upload is read from its own encoded_to() copy, with no concatenation, no unpacking to a byte
         per element and no implied indices, and block-wise updates are accepted. Everything else (ratio below 1, bits
         32, a backend without the method) takes the route above, as with False.
+        sparse_uploads: a round of sparse uploads that carry their per-unit starts — plain (wire v2) or
+        compact (wire v3), bits 32 included — is aggregated from the uploads' own buffers (CodecPlan.aggregate_uploads)
+        where the backend's plan offers it: one pinned copy per received blob, a compact stream read as it is, no
+        concatenation, no unpack launch, no plan per client count. Everything else (wire v1, a dense round, a backend
+        without the method) takes the route above, as with False.
         """
         if not updates:
             return None
@@ -757,6 +829,7 @@ class UpdateCodec:
         device = self.backend.default_device() if device is None else torch.device(device)
         # the one-layout plan whose aggregate_dense reads the uploads, when this round takes that route
         one = self.dense_aggregate_plan(h0, device) if dense_kernel else None
+        ups = self.sparse_uploads_plan(updates, device) if sparse_uploads and one is None else None
         if fmt.per_block and one is None:
             raise ValueError("fused aggregation reads per-segment codes: block-wise updates are decoded one by one "
                              "(decode_module), or aggregated by the dense kernel (dense_kernel=True)")
@@ -788,6 +861,12 @@ class UpdateCodec:
             plan = one
             flat = self._aggregate_dense(one, updates, weights, total, base_flat, mode, avg_mask, device,
                                          None if sk is None else sk.flat)
+            if sk is not None and flat.data_ptr() != sk.flat.data_ptr():  # a backend that returns its own buffer
+                sk = root = None
+        elif ups is not None:
+            plan = ups
+            flat = self._aggregate_uploads(ups, updates, weights, total, base_flat, mode, avg_mask, device,
+                                           None if sk is None else sk.flat)
             if sk is not None and flat.data_ptr() != sk.flat.data_ptr():  # a backend that returns its own buffer
                 sk = root = None
         elif sizes:

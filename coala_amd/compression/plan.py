@@ -704,6 +704,87 @@ class CodecPlan:
         _lib.check(rc, "coalac_aggregate_dense")
         return out  # ptrs / w / m were allocated on the launch stream: their memory is reused only after the kernel
 
+    AGG_UPLOAD_KINDS = {"entries": _lib.COALAC_AGGS_ENTRIES, "compact": _lib.COALAC_AGGS_COMPACT}
+
+    def aggregate_uploads(self, idxs, packeds, vals, mns, scales, ustarts, weights, total=None, base=None, out=None,
+                          mode="recip", avg_mask=None, kind="entries", stream=None):
+        """aggregate() of C sparse uploads of THIS plan's layout (a one-client sparse plan), each read from its own
+        buffers (coalac_aggregate_uploads): no concatenation, no `clients`-copies plan. Lists of C
+        tensors, one per upload (a list the kind does not read may be None) —
+
+            kind "entries": idxs int32[total_k], vals uint8[total_k] (bits 32: fp32[total_k])      (wire v2)
+            kind "compact": packeds uint32[packed_words], the wire v3 stream; vals fp32[total_k] at bits 32 only
+
+        mns / scales: fp32[n_segments] each (not read at bits 32, may be None); ustarts: int32[n_units] each, the
+        per-unit starts. weights, total, base, mode, avg_mask and the result as aggregate(): out fp32[span] indexed by
+        the plan's segments, bit-identical to unpack (compact) and aggregate on the concatenated uploads. The pointer
+        arrays, the weights and the mask go up in small copies on the launch stream. Asynchronous on `stream`."""
+        if self.dense:
+            raise ValueError("aggregate_uploads: a dense plan's uploads are aggregate_dense's")
+        if kind not in self.AGG_UPLOAD_KINDS:
+            raise ValueError(f"kind must be one of {sorted(self.AGG_UPLOAD_KINDS)}, got {kind!r}")
+        modes = {"recip": _lib.COALAC_AGG_RECIP, "div": _lib.COALAC_AGG_DIV, "sum": _lib.COALAC_AGG_SUM}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)}, got {mode!r}")
+        raw, compact = self.bits == 32, kind == "compact"
+        # the lists the kernel reads, in the pointer table's order
+        lists = [("idx", None if compact else idxs, torch.int32, self.total_k),
+                 ("packed", packeds if compact else None, torch.uint32, self.packed_words if compact else 0),
+                 ("vals", vals if raw or not compact else None, self.vals_dtype, self.total_k),
+                 ("mn", None if raw else mns, torch.float32, self.n_segments),
+                 ("scale", None if raw else scales, torch.float32, self.n_segments),
+                 ("ustart", ustarts, torch.int32, self.n_units)]
+        required = {"ustart", "packed" if compact else "idx"} | (set() if raw else {"mn", "scale"}) | \
+            ({"vals"} if raw or not compact else set())
+        C = len(weights)
+        for name, ts, dt, n in lists:
+            if name in required and (ts is None or len(ts) != C):
+                raise ValueError(f"aggregate_uploads: need one {name} tensor per upload ({C} weights), got "
+                                 f"{'none' if ts is None else len(ts)}")
+        if C < 1:
+            raise ValueError("aggregate_uploads: need at least one upload")
+        for name, ts, dt, n in lists:
+            if name not in required:
+                continue
+            for i, t in enumerate(ts):
+                if name == "packed":
+                    self._check_packed(t, f"upload {i}: packed stream")
+                elif name in ("mn", "scale"):
+                    self._check_ranges(f"upload {i}", n, "mn / scale", t)
+                elif t.device != self.device or t.dtype != dt or not t.is_contiguous() or t.numel() < n or \
+                        (name == "ustart" and t.numel() != n):
+                    raise ValueError(f"upload {i}: need {name} as {dt}[{n}] on {self.device}, got "
+                                     f"{t.dtype}[{t.numel()}] on {t.device}")
+                if t.data_ptr() % 4:
+                    raise ValueError(f"upload {i}: the {name} storage must be 4-byte aligned")
+        if avg_mask is not None and len(avg_mask) != self.n_segments:
+            raise ValueError(f"avg_mask: need {self.n_segments} entries, got {len(avg_mask)}")
+        self._check_flat(base, "base")
+        sizes = self.table.segs
+        n_out = int((sizes[:, 0] + sizes[:, 1]).max()) if len(sizes) else 0  # (an output may end with the last segment)
+        with _on(stream):
+            if out is None:
+                out = self.empty_flat() if base is None else torch.empty_like(base)
+            # one table: the pointer arrays the kind reads, C pointers each
+            used = [(name, ts) for name, ts, _, _ in lists if name in required]
+            ptrs = torch.tensor([t.data_ptr() for _, ts in used for t in ts], dtype=torch.int64).to(self.device)
+            w = torch.tensor([float(x) for x in weights], dtype=torch.float64).to(torch.float32).to(self.device)
+            m = None
+            if avg_mask is not None:
+                m = torch.tensor([1 if x else 0 for x in avg_mask], dtype=torch.uint8).to(self.device)
+        self._check_flat(out, "output", n_out)
+        total = float(sum(weights)) if total is None else float(total)
+        at = {name: ctypes.c_void_p(ptrs.data_ptr() + 8 * C * j) for j, (name, _) in enumerate(used)}
+        arr = lambda name: at.get(name, ctypes.c_void_p(None))  # noqa: E731
+        packed_bytes = min(4 * t.numel() for t in packeds) if compact else 0
+        with _device_ctx(self.device):
+            rc = self._lib.coalac_aggregate_uploads(
+                self._h, C, self.AGG_UPLOAD_KINDS[kind], arr("idx"), arr("packed"), ctypes.c_uint64(packed_bytes),
+                arr("vals"), arr("mn"), arr("scale"), arr("ustart"), _ptr(w), ctypes.c_float(total), modes[mode],
+                _ptr(m), _ptr(base), _ptr(out), _stream_handle(stream))
+        _lib.check(rc, "coalac_aggregate_uploads")
+        return out  # ptrs / w / m were allocated on the launch stream: their memory is reused only after the kernel
+
     def implied_indices(self):
         """A dense plan's indices (0..n-1 per segment, every client) as a device int32 tensor, made once."""
         t = self.__dict__.get("_implied")

@@ -345,6 +345,11 @@ class CompressionServerMixin(_CodecOwner):
     # is aggregated by the dense kernel straight from the uploads' own buffers (UpdateCodec.aggregate(...,
     # dense_kernel=True)), block-wise rounds included; off, such rounds go the ways they always went
     codec_fused_dense_aggregate = False
+    # with codec_fused_aggregate: a round of uniform sparse uploads that carry their per-unit starts — plain (wire v2) or
+    # compact (wire v3) — is aggregated from the uploads' own buffers (UpdateCodec.aggregate(..., sparse_uploads=True),
+    # DESIGN.md §17): one pinned copy per received blob, a compact stream read as it is, no concatenation, no unpack
+    # launch and no plan per client count; off, or for any other round, the concatenating route as always
+    codec_fused_sparse_uploads = False
 
     def _decode_upload(self, model):
         base = self._global_snapshot() if model.header["mode"] == "delta" else None
@@ -394,6 +399,7 @@ class CompressionServerMixin(_CodecOwner):
             codec = self._codec()
             dev = codec.backend.default_device()
             dense = bool(self.codec_fused_dense_aggregate)
+            sparse = bool(self.codec_fused_sparse_uploads)
             block = wire.format_of(h0).per_block
             # (a block-wise upload has one range per block, which only the dense kernel reads: without it such a round —
             # and always one of mixed formats — is decoded upload by upload below)
@@ -405,12 +411,12 @@ class CompressionServerMixin(_CodecOwner):
                     dist.barrier()
                     sample_sum = sum(weights)  # weighted_sum returns the caller's sum (0 stays 0)
                     model = codec.aggregate(models, weights, self._real_global(), base=base, mode="sum", device=dev,
-                                            params_only=params_only, dense_kernel=dense)
+                                            params_only=params_only, dense_kernel=dense, sparse_uploads=sparse)
                     reduce_models(params_only)(model, torch.tensor(sample_sum).to(getattr(conf, "device", dev)))
                     return model
                 mode = "div" if dev.type == "cpu" else "recip"  # torch's division semantics on that device
                 return codec.aggregate(models, weights, self._real_global(), base=base, mode=mode, device=dev,
-                                       params_only=params_only, dense_kernel=dense)
+                                       params_only=params_only, dense_kernel=dense, sparse_uploads=sparse)
         models = [self._decode_upload(m) if isinstance(m, CompressedUpdate) else m for m in models]
         parent = getattr(super(), "aggregate", None)
         if parent is not None:

@@ -2540,10 +2540,42 @@ DEV float4 agg_final(float4 a, float total, float inv_total) {
 // Latency: every client's range / mn / scale / weight is fetched lane-parallel in one round (lane j =
 // client j of a 64-client chunk); the first 64 kept entries of AGG_DEPTH clients are then loaded in one
 // batch and accumulated in client order (a unit where some client keeps more than 64 entries takes the
-// unbatched path, one client at a time). Clients are identical copies of one layout, so
-// client c's unit / segment / entry offsets are u + c*U0, seg + c*T, out_off + c*Kc (host-validated).
-template <bool RAW, bool HASBASE, int MODE>
-__global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs A) {
+// unbatched path, one client at a time).
+// Where a client's range and entries come from is the body's SRC:
+//   AGG_STRIDED  one batched plan: the clients are identical copies of one layout, so client c's unit / segment /
+//                entry offsets are u + c*U0, seg + c*T, out_off + c*Kc (host-validated)       — k_aggregate
+//   AGG_ENTRIES  a one-layout plan and per-client pointers: client c's idx / vals / mn / scale / ustart arrays are
+//                where its upload landed. Lane j fetches client j's pointers in a round of their own before the
+//                starts' (they need only the client number); the entries' pointers are read across lanes
+//   AGG_COMPACT  as ENTRIES, the entries being the (12 + B)-bit fields of the client's wire v3 stream: the field's
+//                word and the next (clamped inside the stream), funnel-shifted where they are used; at bits 32 the
+//                fp32 value of entry j is vals[j]                                       — k_aggregate_uploads
+enum { AGG_STRIDED = 0, AGG_ENTRIES = 1, AGG_COMPACT = 2 };
+
+struct AggUploads {  // device arrays of `clients` device pointers each (null where the kind does not read them)
+  const int32_t* const* idx;
+  const uint32_t* const* packed;
+  const void* const* vals;
+  const float* const* mn;
+  const float* const* scale;
+  const uint32_t* const* ustart;
+  uint64_t nwords;  // COMPACT: words of every client's stream
+  uint32_t w;       // COMPACT: field bits, 12 + B
+};
+struct AggNoUploads {};
+
+// a lane's client: where its starts, mn, scale, entries (idx or the stream) and values are
+template <int SRC>
+struct AggClient {
+  const uint32_t* ustart;
+  const float *mn, *scale;
+  const void *ent, *vals;
+};
+template <>
+struct AggClient<AGG_STRIDED> {};
+
+template <int SRC, bool RAW, bool HASBASE, int MODE, class Uploads>
+DEV void aggregate_unit(const Params& P, const AggArgs& A, const Uploads& S) {
   // AGG_SPLIT waves per unit, each owning RI of its UNIT_IT rows: a smaller LDS tile and half the registers
   // per wave, so twice the waves are resident
   constexpr uint32_t RI = UNIT_IT / AGG_SPLIT, HE = UNIT / AGG_SPLIT;  // rows / elements per wave
@@ -2552,11 +2584,35 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
   const uint32_t wid = blockIdx.x * WAVES + wv;
   const uint32_t u = __builtin_amdgcn_readfirstlane(wid / AGG_SPLIT), h = __builtin_amdgcn_readfirstlane(wid % AGG_SPLIT);
   if (u >= A.U0) return;
+  // round 0 (per-client pointers only): lane j's client of the chunk at c0, its pointers
+  AggClient<SRC> C;
+  auto client_of = [&](uint32_t c0) {
+    if constexpr (SRC != AGG_STRIDED) {
+      const uint32_t cl = c0 + min(lane, min(64u, A.clients - c0) - 1);
+      C.ustart = S.ustart[cl];
+      C.mn = RAW ? nullptr : S.mn[cl];
+      C.scale = RAW ? nullptr : S.scale[cl];
+      C.ent = SRC == AGG_COMPACT ? static_cast<const void*>(S.packed[cl]) : static_cast<const void*>(S.idx[cl]);
+      C.vals = SRC == AGG_COMPACT && !RAW ? nullptr : S.vals[cl];
+    }
+  };
+  // the starts of lane j's client in this unit
+  auto starts_of = [&](uint32_t c0, uint32_t& s0, uint32_t& s1) {
+    if constexpr (SRC == AGG_STRIDED) {
+      const uint32_t ucl = u + (c0 + min(lane, min(64u, A.clients - c0) - 1)) * A.U0;
+      s0 = A.ustart[ucl];
+      s1 = A.ustart[min(ucl + 1, P.n_units - 1)];
+    } else {
+      s0 = C.ustart[u];
+      s1 = C.ustart[min(u + 1, P.n_units - 1)];
+    }
+  };
+  client_of(0);
   // round 1: the unit (scalar loads), and the first 64 clients' starts in it (lane j: client j; they need
   // only u), pinned above the first use of either
   const UnitDev U = P.units[u];
-  const uint32_t ucl0 = u + min(lane, min(64u, A.clients) - 1) * A.U0;
-  uint32_t us0 = A.ustart[ucl0], us1 = A.ustart[min(ucl0 + 1, P.n_units - 1)];
+  uint32_t us0, us1;
+  starts_of(0, us0, us1);
   asm volatile("" : "+v"(us0), "+v"(us1)::"memory");
   const uint32_t len = U.len, kseg = U.k;
   const uint32_t e_lo = h * HE;  // first element (within the unit) of this wave's rows
@@ -2586,28 +2642,110 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
     // lane j: client c0 + j (clamped to the last client of the chunk)
     auto meta_of = [&](uint32_t c0, uint32_t s0, uint32_t s1) -> Meta {
       const uint32_t cl = c0 + min(lane, min(64u, A.clients - c0) - 1);
-      const uint32_t sl = U.seg + cl * A.T;
       Meta m;
       m.lo = min(s0, kseg);
       m.hi = max(m.lo, min(min(U.last ? kseg : s1, kseg), m.lo + len));
-      m.mn = RAW ? 0.0f : P.cmn[sl];
-      m.sc = RAW ? 0.0f : P.cscale[sl];
+      if constexpr (SRC == AGG_STRIDED) {
+        const uint32_t sl = U.seg + cl * A.T;
+        m.mn = RAW ? 0.0f : P.cmn[sl];
+        m.sc = RAW ? 0.0f : P.cscale[sl];
+      } else {
+        m.mn = RAW ? 0.0f : C.mn[U.seg];
+        m.sc = RAW ? 0.0f : C.scale[U.seg];
+      }
       m.w = A.weights[cl];
       return m;
     };
     auto meta = [&](uint32_t c0) -> Meta {
-      const uint32_t ucl = u + (c0 + min(lane, min(64u, A.clients - c0) - 1)) * A.U0;
-      return meta_of(c0, A.ustart[ucl], A.ustart[min(ucl + 1, P.n_units - 1)]);
+      uint32_t s0, s1;
+      client_of(c0);
+      starts_of(c0, s0, s1);
+      return meta_of(c0, s0, s1);
+    };
+    // lane jj's pointer, wave-uniform
+    auto lanep = [](const void* p, uint32_t jj) -> const void* {
+      const uint64_t b = reinterpret_cast<uint64_t>(p);
+      const uint32_t l = __builtin_amdgcn_readlane((uint32_t)b, jj), hw = __builtin_amdgcn_readlane((uint32_t)(b >> 32), jj);
+      return reinterpret_cast<const void*>((uint64_t)hw << 32 | l);
+    };
+    // COMPACT: entry e of the unit's segment in a stream, its field's word, the next word inside the stream and
+    // the field's first bit in the word
+    auto field_at = [&](uint32_t e, uint64_t& wd, uint64_t& wd1, uint32_t& sh) {
+      if constexpr (SRC == AGG_COMPACT) {
+        const uint64_t bit = (U.out_off + e) * S.w;
+        wd = bit >> 5;  // (wd < nwords: out_off + e < total_k and the stream holds total_k fields)
+        wd1 = min(wd + 1, S.nwords - 1);
+        sh = (uint32_t)bit & 31u;
+      }
+    };
+    // ... and the entry from the two words: v_alignbit_b32 takes the 32 bits from bit sh of b:a (a itself at
+    // sh == 0). A field that ends inside a takes none of b's bits below the mask; one that straddles has its
+    // second word inside the stream (total_k fields fit nwords words)
+    auto field_entry = [&](uint32_t a, uint32_t b, uint32_t sh, uint32_t raw, uint32_t& idx, uint32_t& q) {
+      if constexpr (SRC == AGG_COMPACT) {
+        const uint32_t v = __builtin_amdgcn_alignbit(b, a, sh) & ((1u << S.w) - 1u);
+        idx = U.start | (v & 0xFFFu);
+        q = RAW ? raw : v >> 12;
+      }
     };
     // entries of client c0 + j: the raw loaded words only (any arithmetic on them here would make the wave
-    // wait for the loads right away, in-order vmcnt)
-    auto fetch = [&](const Meta& M, uint32_t c0, uint32_t j, uint32_t& idx, uint32_t& q) {
+    // wait for the loads right away, in-order vmcnt). COMPACT: the field's two words (x, q), at bits 32 the value (r)
+    auto fetch = [&](const Meta& M, uint32_t c0, uint32_t j, uint32_t& idx, uint32_t& q, uint32_t& r) {
       const uint32_t jj = min(j, min(64u, A.clients - c0) - 1);
+      r = 0;
       const uint32_t lo = __builtin_amdgcn_readlane(M.lo, jj), hi = __builtin_amdgcn_readlane(M.hi, jj);
-      const uint64_t oo = U.out_off + (uint64_t)(c0 + jj) * A.Kc;
+      const uint64_t oo = U.out_off + (SRC == AGG_STRIDED ? (uint64_t)(c0 + jj) * A.Kc : 0);
       const uint32_t e = min(lo + lane, hi > lo ? hi - 1 : lo);  // kseg >= 1: entry lo always exists
-      idx = (uint32_t)P.cidx[oo + min(e, kseg - 1)];
-      q = load_code<RAW>(P, oo + min(e, kseg - 1));
+      if constexpr (SRC == AGG_STRIDED) {
+        idx = (uint32_t)P.cidx[oo + min(e, kseg - 1)];
+        q = load_code<RAW>(P, oo + min(e, kseg - 1));
+      } else if constexpr (SRC == AGG_ENTRIES) {
+        const uint64_t o = oo + min(e, kseg - 1);
+        idx = (uint32_t) static_cast<const int32_t*>(lanep(C.ent, jj))[o];
+        const void* vp = lanep(C.vals, jj);
+        q = RAW ? __float_as_uint(static_cast<const float*>(vp)[o]) : static_cast<const uint8_t*>(vp)[o];
+      } else {
+        const uint32_t* pk = static_cast<const uint32_t*>(lanep(C.ent, jj));
+        uint64_t wd, wd1;
+        uint32_t sh;
+        field_at(min(e, kseg - 1), wd, wd1, sh);
+        idx = pk[wd];
+        q = pk[wd1];
+        if (RAW) r = __float_as_uint(static_cast<const float*>(lanep(C.vals, jj))[oo + min(e, kseg - 1)]);
+      }
+    };
+    // the fetched entry as its index and code (COMPACT: extracted here, where the words are first used)
+    auto entry_of = [&](const Meta& M, uint32_t c0, uint32_t j, uint32_t x, uint32_t y, uint32_t r, uint32_t& idx,
+                        uint32_t& q) {
+      if constexpr (SRC == AGG_COMPACT) {
+        const uint32_t jj = min(j, min(64u, A.clients - c0) - 1);
+        const uint32_t lo = __builtin_amdgcn_readlane(M.lo, jj), hi = __builtin_amdgcn_readlane(M.hi, jj);
+        const uint32_t e = min(min(lo + lane, hi > lo ? hi - 1 : lo), kseg - 1);
+        field_entry(x, y, ((uint32_t)U.out_off + e) * S.w & 31u, r, idx, q);
+      } else {
+        idx = x;
+        q = y;
+      }
+    };
+    // entry e (< kseg) of client c0 + j, loaded and used at once (the generic path)
+    auto entry_at = [&](uint32_t c0, uint32_t j, uint32_t e, uint32_t& idx, uint32_t& q) {
+      if constexpr (SRC == AGG_STRIDED) {
+        const uint64_t oo = U.out_off + (uint64_t)(c0 + j) * A.Kc;
+        idx = (uint32_t)P.cidx[oo + e];
+        q = load_code<RAW>(P, oo + e);
+      } else if constexpr (SRC == AGG_ENTRIES) {
+        const uint64_t o = U.out_off + e;
+        idx = (uint32_t) static_cast<const int32_t*>(lanep(C.ent, j))[o];
+        const void* vp = lanep(C.vals, j);
+        q = RAW ? __float_as_uint(static_cast<const float*>(vp)[o]) : static_cast<const uint8_t*>(vp)[o];
+      } else {
+        const uint32_t* pk = static_cast<const uint32_t*>(lanep(C.ent, j));
+        uint64_t wd, wd1;
+        uint32_t sh, raw = 0;
+        field_at(e, wd, wd1, sh);
+        if (RAW) raw = __float_as_uint(static_cast<const float*>(lanep(C.vals, j))[U.out_off + e]);
+        field_entry(pk[wd], pk[wd1], sh, raw, idx, q);
+      }
     };
     float4 bv[RI];
 #pragma unroll
@@ -2617,9 +2755,9 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
     const uint8_t* amp = A.avg_mask != nullptr ? A.avg_mask + U.seg : reinterpret_cast<const uint8_t*>(A.weights);
     uint32_t am = *amp;
     Meta M = meta_of(0, us0, us1);
-    uint32_t pa[AGG_DEPTH], qa[AGG_DEPTH];
+    uint32_t pa[AGG_DEPTH], qa[AGG_DEPTH], ra[AGG_DEPTH];  // (ra: COMPACT at bits 32 only)
 #pragma unroll
-    for (uint32_t t = 0; t < AGG_DEPTH; ++t) fetch(M, 0, t, pa[t], qa[t]);
+    for (uint32_t t = 0; t < AGG_DEPTH; ++t) fetch(M, 0, t, pa[t], qa[t], ra[t]);
     // pinned: no request above moves below this point (the compiler sinks loads toward their first use,
     // which would put the entries' round behind the base's)
     asm volatile("" : "+v"(M.lo), "+v"(M.hi), "+v"(M.mn), "+v"(M.sc), "+v"(M.w), "+v"(am)::"memory");
@@ -2665,7 +2803,7 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
       if (c0 > 0) {
         M = meta(c0);
 #pragma unroll
-        for (uint32_t t = 0; t < AGG_DEPTH; ++t) fetch(M, c0, t, pa[t], qa[t]);
+        for (uint32_t t = 0; t < AGG_DEPTH; ++t) fetch(M, c0, t, pa[t], qa[t], ra[t]);
       }
       const uint32_t cn = min(64u, nclients - c0);
       // generic path (an odd wave, or any client with more than 64 kept entries in this unit, ratio >~ 1.5 %):
@@ -2675,17 +2813,20 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
         for (uint32_t j = 0; j < cn; ++j) {
           const uint32_t lo = __builtin_amdgcn_readlane(M.lo, j), hi = __builtin_amdgcn_readlane(M.hi, j);
           const float mn = lanef(M.mn, j), sc = lanef(M.sc, j);
-          const uint64_t oo = U.out_off + (uint64_t)(c0 + j) * A.Kc;
           for (uint32_t e = lo + lane; e < hi; e += 64) {
-            const uint32_t p2 = (uint32_t)P.cidx[oo + e] - pbase;
-            const float v2 = load_val<RAW>(P, oo + e, mn, sc);
+            uint32_t ix, q;
+            entry_at(c0, j, e, ix, q);
+            const uint32_t p2 = ix - pbase;
+            const float v2 = code_value<RAW>(q, mn, sc);
             if (p2 < hl) tf[p2] = HASBASE ? bs[p2] + v2 : v2;
           }
           lds_order();
           accumulate(lanef(M.w, j));
           lds_order();
           for (uint32_t e = lo + lane; e < hi; e += 64) {
-            const uint32_t p2 = (uint32_t)P.cidx[oo + e] - pbase;
+            uint32_t ix, q;
+            entry_at(c0, j, e, ix, q);
+            const uint32_t p2 = ix - pbase;
             if (p2 < hl) tf[p2] = HASBASE ? bs[p2] + 0.0f : 0.0f;
           }
           lds_order();
@@ -2698,23 +2839,30 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
       for (uint32_t j0 = 0; j0 < cn; j0 += AGG_DEPTH) {
         if (j0 > 0) {
 #pragma unroll
-          for (uint32_t t = 0; t < AGG_DEPTH; ++t) fetch(M, c0, j0 + t, pa[t], qa[t]);
+          for (uint32_t t = 0; t < AGG_DEPTH; ++t) fetch(M, c0, j0 + t, pa[t], qa[t], ra[t]);
         }
-        float tb = HASBASE ? tf[min(pa[0] - pbase, HE - 1)] : 0.0f;
+        uint32_t ix, q, ixn = 0, qn = 0;
+        entry_of(M, c0, j0, pa[0], qa[0], ra[0], ix, q);
+        float tb = HASBASE ? tf[min(ix - pbase, HE - 1)] : 0.0f;
 #pragma unroll
         for (uint32_t t = 0; t < AGG_DEPTH; ++t) {
           const uint32_t j = j0 + t;
           if (j >= cn) continue;
-          const uint32_t pos = pa[t] - pbase;  // wraps (>= hl) outside this wave's rows
+          if constexpr (SRC != AGG_COMPACT)
+            entry_of(M, c0, j, pa[t], qa[t], ra[t], ix, q);  // (the loaded words themselves)
+          else if (t > 0)
+            ix = ixn, q = qn;  // (extracted once, for the tile value read under it)
+          const uint32_t pos = ix - pbase;  // wraps (>= hl) outside this wave's rows
           const uint32_t ne = __builtin_amdgcn_readlane(M.hi, j) - __builtin_amdgcn_readlane(M.lo, j);
           const bool mine = lane < ne && pos < hl;
-          const float d = code_value<RAW>(qa[t], lanef(M.mn, j), lanef(M.sc, j));
+          const float d = code_value<RAW>(q, lanef(M.mn, j), lanef(M.sc, j));
           if (mine) tf[pos] = HASBASE ? tb + d : d;
           lds_order();
           accumulate(lanef(M.w, j));
           lds_order();
           if (mine) tf[pos] = tb;
-          if (HASBASE && t + 1 < AGG_DEPTH) tb = tf[min(pa[t + 1] - pbase, HE - 1)];
+          if (t + 1 < AGG_DEPTH) entry_of(M, c0, j + 1, pa[t + 1], qa[t + 1], ra[t + 1], ixn, qn);
+          if (HASBASE && t + 1 < AGG_DEPTH) tb = tf[min(ixn - pbase, HE - 1)];
           lds_order();
         }
       }
@@ -2738,6 +2886,18 @@ __global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs 
     body(std::true_type{});
   else
     body(std::false_type{});
+}
+
+template <bool RAW, bool HASBASE, int MODE>
+__global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate(Params P, AggArgs A) {
+  aggregate_unit<AGG_STRIDED, RAW, HASBASE, MODE>(P, A, AggNoUploads{});
+}
+
+// k_aggregate's body over a one-layout plan, every client's arrays where its upload landed (A.U0 = the plan's units;
+// A.ustart, A.T and A.Kc are not read). SRC: AGG_ENTRIES or AGG_COMPACT
+template <int SRC, bool RAW, bool HASBASE, int MODE>
+__global__ __launch_bounds__(BLOCK, AGG_WPE) void k_aggregate_uploads(Params P, AggArgs A, AggUploads S) {
+  aggregate_unit<SRC, RAW, HASBASE, MODE>(P, A, S);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4603,6 +4763,73 @@ int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void
     launch(std::integral_constant<int, COALAC_AGGD_PACKED>{});
   else
     launch(std::integral_constant<int, COALAC_AGGD_BLOCK>{});
+  return launched();
+}
+
+int coalac_aggregate_uploads(coalac_plan_t plan, int clients, int kind, const int32_t* const* d_idx,
+                             const void* const* d_packed, uint64_t packed_bytes, const void* const* d_vals,
+                             const float* const* d_mn, const float* const* d_scale, const uint32_t* const* d_ustart,
+                             const float* d_weights, float total, int mode, const uint8_t* d_avg_mask,
+                             const float* d_base, float* d_out, void* stream) {
+  const char* who = "coalac_aggregate_uploads";
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  // (a plan without units is dense by definition and has nothing to aggregate: OK below)
+  if (plan->dense && plan->proto.n_units)
+    return fail(COALAC_EINVAL, "%s: a dense plan (every k == n) is coalac_aggregate_dense's", who);
+  if (clients < 1) return fail(COALAC_EINVAL, "%s: clients=%d, need at least 1", who, clients);
+  if (kind != COALAC_AGGS_ENTRIES && kind != COALAC_AGGS_COMPACT) return fail(COALAC_EINVAL, "%s: bad kind %d", who, kind);
+  if (mode != COALAC_AGG_DIV && mode != COALAC_AGG_RECIP && mode != COALAC_AGG_SUM)
+    return fail(COALAC_EINVAL, "%s: bad mode %d", who, mode);
+  if (plan->proto.n_units == 0) return COALAC_OK;
+  const bool raw = plan->bits == 32, compact = kind == COALAC_AGGS_COMPACT;
+  if (!d_ustart || !d_weights || !d_out) return fail(COALAC_EINVAL, "%s: ustart/weights/output pointer is NULL", who);
+  if (compact ? !d_packed : !d_idx) return fail(COALAC_EINVAL, "%s: the %s pointer array is NULL", who, compact ? "packed" : "idx");
+  if ((!compact || raw) && !d_vals) return fail(COALAC_EINVAL, "%s: the vals pointer array is NULL", who);
+  if (!raw && (!d_mn || !d_scale)) return fail(COALAC_EINVAL, "%s: mn/scale pointer arrays are NULL", who);
+  const uint64_t need = 4 * packed_words(plan);
+  if (compact && packed_bytes < need)
+    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
+                (unsigned long long)need);
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "%s: output/base must be 16-byte aligned", who);
+  if ((addr_bits(d_idx, d_packed, d_vals) | addr_bits(d_mn, d_scale, d_ustart)) & 7 || addr_bits(d_weights) & 3)
+    return fail(COALAC_EINVAL, "%s: the pointer arrays must be 8-byte, the weights 4-byte aligned", who);
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  AggArgs A{};
+  A.weights = d_weights;
+  A.clients = (uint32_t)clients;
+  A.T = P.nseg;
+  A.U0 = P.n_units;
+  A.total = total;
+  A.inv_total = 1.0f / total;
+  A.avg_mask = d_avg_mask;
+  AggUploads S{};
+  S.idx = d_idx;
+  S.packed = reinterpret_cast<const uint32_t* const*>(d_packed);
+  S.vals = d_vals;
+  S.mn = d_mn;
+  S.scale = d_scale;
+  S.ustart = d_ustart;
+  S.nwords = packed_bytes / 4;
+  S.w = packed_field_bits(plan);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto launch = [&](auto src) {
+    with_flags(
+        [&](auto rw, auto hb) {
+          with_agg_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL((k_aggregate_uploads<decltype(src)::value, rw.value, hb.value, m.value>),
+                               dim3(ceil_div(P.n_units * AGG_SPLIT, WAVES)), dim3(BLOCK), 0, st, P, A, S);
+          });
+        },
+        raw, d_base != nullptr);
+  };
+  if (compact)
+    launch(std::integral_constant<int, AGG_COMPACT>{});
+  else
+    launch(std::integral_constant<int, AGG_ENTRIES>{});
   return launched();
 }
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define COALAC_ABI_VERSION 10
+#define COALAC_ABI_VERSION 11
 
 enum {
   COALAC_OK = 0,
@@ -67,7 +67,9 @@ enum {
  * coalac_encode_block / coalac_decode_block — one quantisation range per 4096-element unit of a dense plan, encoded in
  * one pass into the wire v4 code stream (wire v5); every existing entry point, query and size is as it was. ABI 10 adds
  * the one entry point coalac_aggregate_dense — the fused decode + FedAvg of ratio-1 uploads read from their own uint8
- * codes, wire v4 streams or block-wise (wire v5) streams; nothing that existed changes.) */
+ * codes, wire v4 streams or block-wise (wire v5) streams; nothing that existed changes. ABI 11 adds the one entry point
+ * coalac_aggregate_uploads — the sparse fused decode + FedAvg read from each upload's own idx / vals arrays or wire v3
+ * stream; nothing that existed changes.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -309,6 +311,39 @@ enum { COALAC_AGGD_CODES = 0, COALAC_AGGD_PACKED = 1, COALAC_AGGD_BLOCK = 2 };
 int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void* const* d_codes, uint64_t code_bytes,
                            const float* const* d_mn, const float* const* d_scale, const float* d_weights, float total,
                            int mode, const uint8_t* d_avg_mask, const float* d_base, float* d_out, void* stream);
+
+/* coalac_aggregate from each SPARSE upload's own buffers. `plan` is a ONE-LAYOUT sparse plan (not dense;
+ * bits 1..8 or 32): d_out / d_base are indexed by its in_off. The arithmetic is coalac_aggregate's contract bit for bit
+ * (x_i = base + d_i, +0.0f where client i kept nothing; acc = x_0 * w_0, acc = acc + x_i * w_i in client order, no FMA;
+ * DIV | RECIP | SUM; an unmasked segment gets x_0; the forms for a -0.0f or NaN base carry over). kind says what client
+ * i's entries are:
+ *   COALAC_AGGS_ENTRIES  d_idx[i]: int32[total_k], d_vals[i]: uint8[total_k] codes (bits 1..8) or fp32[total_k] (bits 32)
+ *                        — an upload as coalac_encode wrote it (wire v2); d_packed is ignored
+ *   COALAC_AGGS_COMPACT  d_packed[i]: the wire v3 stream above (packed_bytes long each): for unit u and every entry
+ *                        position j = out_off_s + e, e in the unit's clamped range [ustart[u], ustart[u + 1]) (the clamp
+ *                        coalac_decode, coalac_unpack and coalac_aggregate share), the field's in-unit position is
+ *                        field_j & 0xFFF and its code field_j >> 12; the field's second word is read only inside
+ *                        packed_bytes. d_idx is ignored (may be NULL); d_vals[i]: fp32[total_k] at bits 32, else ignored
+ * An entry whose position lies outside the unit's elements is dropped (both kinds). On any payload validate() accepts the
+ * result equals coalac_unpack of every upload followed by coalac_aggregate on their concatenation.
+ * d_idx, d_packed, d_vals, d_mn, d_scale, d_ustart: DEVICE arrays of `clients` device pointers, as
+ * coalac_aggregate_dense takes them; d_mn[i] / d_scale[i]: fp32[nseg] (bits 32: unused, may be NULL); d_ustart[i]:
+ * uint32[n_units], required. d_weights: DEVICE fp32[clients]; d_avg_mask: DEVICE uint8[nseg] or NULL. Only the segments'
+ * elements of d_out are written. One asynchronous launch on `stream`: no allocation, no workspace, no host
+ * synchronisation; any `clients` >= 1.
+ * COALAC_EINVAL (with a coalac_last_error message): a dense plan (coalac_aggregate_dense's), clients < 1, a bad kind or
+ * mode, a required array NULL, a packed_bytes below coalac_plan_packed_bytes (COMPACT), d_out / d_base not 16-byte
+ * aligned. A plan without units returns COALAC_OK and launches nothing. The CONTENTS of the pointer arrays are the
+ * caller's duty: every pointer 4-byte aligned and its array as long as stated (coala_amd/compression/plan.py
+ * aggregate_uploads checks each tensor). An untrusted upload can mis-aggregate, but the kernel never writes outside the
+ * unit's elements and never reads outside [d_packed[i], + packed_bytes), idx / vals [0, total_k), mn / scale [0, nseg) or
+ * ustart [0, n_units). */
+enum { COALAC_AGGS_ENTRIES = 0, COALAC_AGGS_COMPACT = 1 };
+int coalac_aggregate_uploads(coalac_plan_t plan, int clients, int kind, const int32_t* const* d_idx,
+                             const void* const* d_packed, uint64_t packed_bytes, const void* const* d_vals,
+                             const float* const* d_mn, const float* const* d_scale, const uint32_t* const* d_ustart,
+                             const float* d_weights, float total, int mode, const uint8_t* d_avg_mask,
+                             const float* d_base, float* d_out, void* stream);
 
 /* Snapshot n scalars of elem_bytes (1, 2, 4 or 8) each, read through the DEVICE pointer array d_src (each pointer
  * aligned to elem_bytes), into the contiguous d_out, in one launch on `stream`: the passthrough entries of an
