@@ -84,11 +84,23 @@ def even(lens, k):
 def place(style, length, cnt, rng, c, C):
     """cnt ascending unique positions of a unit of `length` elements. Styles: any; upper / lower (one wave's half
     only, where it has room); edges (0, 2047, 2048, length - 1 first, client c starting at the c-th of them);
-    disjoint (client c owns the positions c mod C, where they suffice)."""
+    disjoint (client c owns the positions c mod C, where they suffice). For the decode's tile passes
+    (tests/decode_inputs.py): seams (0, every multiple of 1024 with its predecessor, length - 1 first); last
+    (length - 1 first); passQ (only [1024 Q, 1024 (Q + 1)), where it has room); twins (pass0); twins_last (only the
+    1024-element stretch that holds length - 1, where it has room)."""
     if cnt == 0:
         return np.zeros(0, np.int64)
     pool = np.arange(length)
-    if style == "upper" and length - 2048 >= cnt:
+    if style in ("seams", "last"):
+        e = [length - 1] if style == "last" else [0] + [p for m in range(1024, length, 1024) for p in (m - 1, m)] + [length - 1]
+        e = list(dict.fromkeys(e))[:cnt]
+        more = rng.choice(np.setdiff1d(pool, e), cnt - len(e), replace=False) if cnt > len(e) else []
+        return np.sort(np.concatenate([e, more]).astype(np.int64))
+    if style in ("twins", "twins_last") or style.startswith("pass"):
+        q = 0 if style == "twins" else (length - 1) // 1024 if style == "twins_last" else int(style[4:])
+        if min(length, 1024 * (q + 1)) - 1024 * q >= cnt:
+            pool = np.arange(1024 * q, min(length, 1024 * (q + 1)))
+    elif style == "upper" and length - 2048 >= cnt:
         pool = np.arange(2048, length)
     elif style == "lower" and min(length, 2048) >= cnt:
         pool = np.arange(min(length, 2048))

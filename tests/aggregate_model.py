@@ -65,6 +65,28 @@ def decode_client_segment(idx, vals, mn, scale, ustart, g0, n_units, n, k, oo, b
         return np.ascontiguousarray(base, dtype=F32) + d
 
 
+def decode(idx, vals, mn, scale, ustart, segs, bits, out, base=None, segments=None):
+    """coalac_decode (k_decode_lds) of a payload with the given starts into `out` (fp32, any fill): only the
+    segments' elements are written, so a sentinel-filled `out` becomes the expected whole buffer. segs: the plan's
+    [T, 4] rows; base: fp32 indexed like out, or None; segments: the rows to decode (default: all — the others' units
+    are still counted past, their elements and counts left as they are). Returns Counts (units: int64[n_units, 2]);
+    raises RacyPayload where the GPU result is undefined."""
+    segs = np.asarray(segs, dtype=np.int64).reshape(-1, 4)
+    idx = np.asarray(idx).astype(np.int64) & M32
+    ustart = np.asarray(ustart).astype(np.int64) & M32
+    n_units = int(ustart.size)
+    nus = [units_of(n) for n in segs[:, 1]]
+    ubeg = np.concatenate([[0], np.cumsum(nus)]).astype(np.int64)
+    assert int(ubeg[-1]) == n_units, "starts do not match the layout"
+    units = np.zeros((n_units, 2), dtype=np.int64)
+    for s in range(len(segs)) if segments is None else segments:
+        off, n, k, oo = (int(v) for v in segs[s])
+        b = None if base is None else base[off:off + n]
+        out[off:off + n] = decode_client_segment(idx, vals, mn[s], scale[s], ustart, int(ubeg[s]), n_units, n, k, oo,
+                                                 bits, b, units[ubeg[s]:ubeg[s + 1]])
+    return Counts(int(units[:, 0].sum()), int(units[:, 1].sum()), units)
+
+
 def aggregate(idx, vals, mn, scale, ustart, segs, bits, clients, weights, total, mode, out, base=None,
               avg_mask=None):
     """coalac_aggregate of a payload with the given starts into `out` (fp32, any fill): only the elements of client
