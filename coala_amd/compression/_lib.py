@@ -66,6 +66,10 @@ SIGNATURES = [
     # packed_bytes, bmn, bscale, base, out, stream
     ("coalac_encode_block", _I, [_P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     ("coalac_decode_block", _I, [_P, _P, _U64, _P, _P, _P, _P, _P]),
+    # stochastic rounding: plan, in, seg pointers, base, vals, mn, scale, ws, ws_bytes, seed, flags, stream / plan, in,
+    # seg pointers, base, bmn, bscale, packed, packed_bytes, seed, stream
+    ("coalac_encode_sr", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _U64, _U64, ctypes.c_uint, _P]),
+    ("coalac_encode_block_sr", _I, [_P, _P, _P, _P, _P, _P, _P, _U64, _U64, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -83,6 +87,9 @@ SIGNATURES = [
 ]
 
 ABI_VERSION = 11
+# added without a version step (purely additive): a library of the same ABI version built before them (a COALAC_LIB
+# variant of an earlier commit) loads without them, and only a call that needs one fails
+ADDED_IN_ABI_11 = ("coalac_encode_sr", "coalac_encode_block_sr")
 
 
 class CodecError(RuntimeError):
@@ -124,6 +131,8 @@ def load(build_if_missing=True):
         if v != ABI_VERSION:
             raise CodecError(f"libcoalac ABI version {v} != expected {ABI_VERSION} ({path}: rebuild it from this tree)")
         for name, res, args in SIGNATURES:
+            if name in ADDED_IN_ABI_11 and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

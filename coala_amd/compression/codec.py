@@ -18,6 +18,7 @@ State / layout description: state.py; blob validation: validate.py; decoded-modu
 """
 import ctypes
 import math
+import os
 import threading
 from collections import OrderedDict
 
@@ -29,7 +30,7 @@ from . import _lib, wire
 from ._cache import IdentityCache
 from .clone import _recipe, _reuse_after, _segment_views, module_with_state, release_decode_pool
 from .plan import CodecPlan, Encoded
-from .spec import RAW_BITS, UNIT, VALID_BITS
+from .spec import RAW_BITS, UNIT, VALID_BITS, sr_call_seed
 from .state import (FlatState, RawState, as_numpy, describe_state, describe_tensors,  # noqa: F401 (re-exported)
                     flatten_state, layout_of, module_tensors)
 from .state import (_check_same_layout, _data_ptr, _decode_layout, _dense_elements, _describe, _get_device,
@@ -371,10 +372,18 @@ class UpdateCodec:
                sets the step of its whole tensor; the codes always travel bit-packed, and the encode is one pass over
                the update. Applies where pack_dense applies (and wins over it when both are set); below ratio 1 or at
                bits 32 it is ignored. Not combinable with error feedback (residual=). Off by default.
+        stochastic: ratio-1 (dense) updates with bits 1..8 — per-tensor or block-wise — are quantised with stochastic
+               (unbiased) rounding: a code is floor(t) or floor(t) + 1 with probability equal to the
+               fraction, so the decoded value is an unbiased estimate and the error of an average of C such updates
+               falls as 1 / sqrt(C) instead of staying at the round-to-nearest bias. The payload formats do not change
+               (rounding mode is not on the wire). Only the dense family has it: a ratio below 1, bits 32, a residual=
+               or a backend without the stochastic encodes is a ValueError, not silently ignored. Off by default.
+        seed:  the 64-bit seed of the stochastic rounding; the n-th stochastic encode of this codec uses
+               spec.sr_call_seed(seed, n). None draws it from os.urandom once per codec.
     """
 
     def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True, compact=False, pack_dense=False,
-                 blockwise=False):
+                 blockwise=False, stochastic=False, seed=None):
         if not (0.0 < float(ratio) <= 1.0):
             raise ValueError(f"ratio must be in (0, 1], got {ratio}")
         if bits not in VALID_BITS:
@@ -386,6 +395,15 @@ class UpdateCodec:
         self.compact = bool(compact)
         self.pack_dense = bool(pack_dense)
         self.blockwise = bool(blockwise)
+        self.stochastic = bool(stochastic)
+        if self.stochastic:
+            if self.ratio < 1.0:
+                raise ValueError(f"stochastic rounding covers the dense quantisers only (ratio 1), got ratio {ratio}: "
+                                 "the sparse top-k emit rounds to nearest")
+            if self.bits == RAW_BITS:
+                raise ValueError("stochastic rounding needs bits 1..8: bits 32 carries the fp32 values, nothing is rounded")
+        self.seed = (int.from_bytes(os.urandom(8), "little") if seed is None else int(seed)) & ((1 << 64) - 1)
+        self._sr_calls = 0  # stochastic encodes so far (under _lock: a server encodes from several threads)
         self.backend = backend if backend is not None else HipBackend()
         self._plans = {}
         self._plan_fast = IdentityCache(32)  # (sizes object; ratio, bits, clients, device) -> plan
@@ -409,6 +427,13 @@ class UpdateCodec:
                 p = self.backend.make_plan(list(sizes), ratio, bits, device, clients=clients)
                 self._plans[key] = p
         return p
+
+    def _next_sr_seed(self):
+        """The seed of this codec's next stochastic encode: sr_call_seed(seed, n), n counted under the lock."""
+        with self._lock:
+            n = self._sr_calls
+            self._sr_calls = n + 1
+        return sr_call_seed(self.seed, n)
 
     @staticmethod
     def release_pool():
@@ -487,6 +512,16 @@ class UpdateCodec:
             if getattr(plan, "encode_block", None) is None:
                 raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
                                    "has no encode_block: block-wise quantisation is not available on it")
+        sr_seed = None
+        if self.stochastic:
+            if residual is not None:
+                raise ValueError("stochastic rounding cannot be combined with error feedback (residual=): the residual "
+                                 "already returns the quantisation error to the client")
+            need = "encode_block_sr" if blockwise else "encode_sr"
+            if getattr(plan, need, None) is None or not _all_kept(plan):
+                raise ValueError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
+                                 f"has no {need}: stochastic rounding is not available on it")
+            sr_seed = self._next_sr_seed()
         if residual is not None:
             if getattr(plan, "ef_accumulate", None) is None or getattr(plan, "ef_commit", None) is None:
                 raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
@@ -516,11 +551,12 @@ class UpdateCodec:
                     self._checked_ptrs[id(plan)] = ptrs
         if blockwise:
             # wire v5: one pass — ranges per block, the bit-packed stream written directly (no workspace, no codes)
+            block, how = (plan.encode_block, {}) if sr_seed is None else (plan.encode_block_sr, {"seed": sr_seed})
             if in_place:
-                bmn, bscale, packed = plan.encode_block(tensors=segs, base=base_flat, stream=cur, checked=True, ptrs=ptrs)
+                bmn, bscale, packed = block(tensors=segs, base=base_flat, stream=cur, checked=True, ptrs=ptrs, **how)
             else:
-                bmn, bscale, packed = plan.encode_block(flat=flatten_state(state_fn(), device=device).flat,
-                                                        base=base_flat, stream=cur)
+                bmn, bscale, packed = block(flat=flatten_state(state_fn(), device=device).flat, base=base_flat,
+                                            stream=cur, **how)
             header.update(total_k=int(plan.table.total_k), blockwise=UNIT, n_blocks=int(plan.table.n_units))
             enc = Encoded(torch.empty(0, dtype=torch.int32, device=bmn.device), None, bmn, bscale, None, packed)
             return CompressedUpdate(header, enc, raw() if callable(raw) else raw, packed=packed)
@@ -533,6 +569,13 @@ class UpdateCodec:
                 plan.ef_accumulate(residual, flat=flatten_state(state_fn(), device=device).flat, base=base_flat)
             enc = plan.encode(residual, base=None, workspace=ws)
             plan.ef_commit(enc, residual)
+        elif sr_seed is not None:  # the dense encode with stochastic rounding, from the same two sources
+            if in_place:
+                enc = plan.encode_sr(tensors=segs, base=base_flat, seed=sr_seed, workspace=ws, stream=cur, checked=True,
+                                     ptrs=ptrs)
+            else:
+                enc = plan.encode_sr(flat=flatten_state(state_fn(), device=device).flat, base=base_flat, seed=sr_seed,
+                                     workspace=ws, stream=cur)
         elif in_place:  # read the parameters where they live: no flattening copy (+8 B/element of traffic)
             # (dtype and sizes hold by construction: the plan was made from this layout's segments)
             enc = plan.encode_segments(segs, base=base_flat, workspace=ws, checked=True, ptrs=ptrs, launch=cur)

@@ -286,6 +286,37 @@ class CodecPlan:
         _lib.check(rc, "coalac_encode_segptr")
         return out
 
+    def encode_sr(self, flat=None, tensors=None, base=None, seed=0, out=None, workspace=None, flags=0, stream=None,
+                  checked=False, ptrs=None):
+        """The dense (every k == n, bits 1..8) encode with stochastic (unbiased) rounding (coalac_encode_sr, DESIGN.md
+        §18): mn / scale as encode() computes them, every code floor(t) or floor(t) + 1 by a hash of `seed` (64 bits)
+        and the element's position — the same seed gives the same codes, from `flat` (fp32[span]) as from `tensors`
+        (one per segment, as encode_segments reads them); exactly one of the two. base, out, workspace as encode();
+        idx and the per-unit starts are implied and not written. Asynchronous on `stream`."""
+        self._need_dense("encode_sr")
+        if (flat is None) == (tensors is None):
+            raise ValueError("encode_sr: give exactly one of flat and tensors")
+        self._check_flat(base, "base")
+        launch = torch.cuda.current_stream(self.device) if stream is None else stream
+        if tensors is not None:
+            seg, x = _ptr(self.segment_pointers(tensors, checked=checked, ptrs=ptrs, stream=launch)), _ptr(None)
+        else:
+            self._check_flat(flat, "input")
+            seg, x = _ptr(None), _ptr(flat)
+        with _on(stream):
+            out = self.empty_encoded(with_idx=False) if out is None else out
+            ws = self.empty_workspace() if workspace is None else workspace
+        self._check_encoded(out)
+        if ws.device != self.device or ws.numel() * ws.element_size() < self.ws_bytes:
+            raise ValueError(f"workspace: need {self.ws_bytes} bytes on {self.device}")
+        fn = self._sr_entry("coalac_encode_sr")
+        with _device_ctx(self.device):
+            rc = fn(self._h, x, seg, _ptr(base), _ptr(out.vals), _ptr(out.mn), _ptr(out.scale), _ptr(ws),
+                    ctypes.c_uint64(self.ws_bytes), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                    ctypes.c_uint(flags), ctypes.c_void_p(launch.cuda_stream))
+        _lib.check(rc, "coalac_encode_sr")
+        return out
+
     # -- error feedback ---------------------------------------------------------------------------
     def ef_accumulate(self, resid, flat=None, tensors=None, base=None, stream=None, checked=False, ptrs=None):
         """resid = (x - base) + resid over every segment (coalac_ef_accumulate; fp32 subtract then add, base None:
@@ -496,9 +527,26 @@ class CodecPlan:
         stream in wire v4's layout. The update is read from `flat` (fp32[span]) or from `tensors` (one per segment, as
         encode_segments reads them) — exactly one of the two; base: flat fp32[span] (delta mode). out: such a triple
         to write into. Asynchronous on `stream`."""
-        self._need_dense("encode_block")
+        return self._encode_block("encode_block", None, flat, tensors, base, out, stream, checked, ptrs)
+
+    def encode_block_sr(self, flat=None, tensors=None, base=None, seed=0, out=None, stream=None, checked=False,
+                        ptrs=None):
+        """encode_block with stochastic (unbiased) rounding (coalac_encode_block_sr): the same ranges,
+        every code floor(t) or floor(t) + 1 by a hash of `seed` (64 bits) and the element's position — the same seed
+        gives the same stream, and decode_block / aggregate_dense read it as any other."""
+        return self._encode_block("encode_block_sr", seed, flat, tensors, base, out, stream, checked, ptrs)
+
+    def _sr_entry(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise _lib.CodecError(f"the loaded codec library has no {name} (built before stochastic rounding)")
+        return fn
+
+    def _encode_block(self, who, seed, flat, tensors, base, out, stream, checked, ptrs):
+        # encode_block / encode_block_sr (seed None: the deterministic entry point)
+        self._need_dense(who)
         if (flat is None) == (tensors is None):
-            raise ValueError("encode_block: give exactly one of flat and tensors")
+            raise ValueError(f"{who}: give exactly one of flat and tensors")
         self._check_flat(base, "base")
         launch = torch.cuda.current_stream(self.device) if stream is None else stream
         if tensors is not None:
@@ -510,12 +558,18 @@ class CodecPlan:
             with _on(stream):
                 out = self.empty_block_encoded()
         bmn, bscale, packed = out
-        self._check_ranges("encode_block", self.n_units, "bmn / bscale", bmn, bscale)
+        self._check_ranges(who, self.n_units, "bmn / bscale", bmn, bscale)
         self._check_dense_packed(packed, "packed output")
-        with _device_ctx(self.device):
-            rc = self._lib.coalac_encode_block(self._h, x, seg, _ptr(base), _ptr(bmn), _ptr(bscale), _ptr(packed),
-                                               ctypes.c_uint64(4 * packed.numel()), ctypes.c_void_p(launch.cuda_stream))
-        _lib.check(rc, "coalac_encode_block")
+        args = (self._h, x, seg, _ptr(base), _ptr(bmn), _ptr(bscale), _ptr(packed), ctypes.c_uint64(4 * packed.numel()))
+        st = ctypes.c_void_p(launch.cuda_stream)
+        if seed is None:
+            with _device_ctx(self.device):
+                rc = self._lib.coalac_encode_block(*args, st)
+        else:
+            fn = self._sr_entry("coalac_encode_block_sr")
+            with _device_ctx(self.device):
+                rc = fn(*args, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), st)
+        _lib.check(rc, "coalac_" + who)
         return bmn, bscale, packed
 
     def decode_block(self, packed, bmn, bscale, base=None, out=None, stream=None):

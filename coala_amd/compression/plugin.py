@@ -39,6 +39,10 @@ Behaviour:
     = True` on a client for a ratio-1 upload; any bits <= 8): one min / scale pair per 4096-element block instead of
     one per tensor, the codes bit-packed (wire v5). Self-describing; such uploads are decoded one by
     one, not fused; not combinable with error feedback.
+  * stochastic rounding (opt-in, `codec_stochastic = True` on a client for a ratio-1 upload, `codec_download_stochastic =
+    True` on the server for the download; bits 1..8, per-tensor or block-wise): unbiased codes, so the error of the
+    server's average falls as 1 / sqrt(clients). The payload formats are unchanged; not combinable with
+    error feedback.
   * calculate_model_size(): reports the real payload size for a carrier (base.py:155, 474-487).
   * server decompression(model): CompressedUpdate -> a NEW nn.Module (never aliases self.model, which
     aggregation overwrites, base.py:571) built on the pre-aggregation global model (delta mode: w_global
@@ -63,12 +67,14 @@ Behaviour:
 import copy
 import pickle
 import threading
+import zlib
 
 from torch import nn
 
 from . import wire
 from .codec import CompressedUpdate, UpdateCodec, _uniform
 from .download import CompressedModel, compress_model
+from .spec import sr_call_seed
 from .state import _layout_walk, _module_walk
 
 DATA_TYPE_FEATURE = 2  # coala/pb/common.proto: DataType.DATA_TYPE_FEATURE (protos/coala/pb/common.proto:26)
@@ -117,13 +123,28 @@ class _CodecOwner:
                              "reads per-segment codes, a block-wise payload has one range per 4096-element block")
         return on
 
+    def _codec_stochastic(self):
+        """(codec_stochastic, its seed). Refused next to codec_error_feedback: the residual already returns the
+        quantisation error. An integer seed is folded with the client's cid when it has one — sr_call_seed(seed, hash of
+        cid) — so two clients configured alike do not round alike (identical seeds would cancel the averaging gain)."""
+        on = bool(getattr(self, "codec_stochastic", False))
+        if on and getattr(self, "codec_error_feedback", False):
+            raise ValueError("codec_stochastic cannot be combined with codec_error_feedback: error feedback already "
+                             "returns the quantisation error to the client")
+        seed = getattr(self, "codec_stochastic_seed", None)
+        cid = getattr(self, "cid", None)
+        if on and seed is not None and cid is not None:
+            seed = sr_call_seed(seed, zlib.crc32(repr(cid).encode()))
+        return on, seed
+
     def _codec(self):
         c = self.__dict__.get("_update_codec")
         if c is None:
+            stochastic, seed = self._codec_stochastic()
             c = UpdateCodec(self.codec_ratio, self.codec_bits, self.codec_mode, self.codec_backend,
                             recycle=self.codec_recycle, compact=getattr(self, "codec_compact", False),
                             pack_dense=getattr(self, "codec_pack_dense", False),
-                            blockwise=self._codec_blockwise())
+                            blockwise=self._codec_blockwise(), stochastic=stochastic, seed=seed)
             self.__dict__["_update_codec"] = c
         return c
 
@@ -154,6 +175,14 @@ class CompressionClientMixin(_CodecOwner):
     # instead of one per tensor, the codes always bit-packed. Applies where codec_pack_dense applies (bits 8 included)
     # and wins over it; self-describing. Not combinable with codec_error_feedback (ValueError). Off by default.
     codec_blockwise = False
+
+    # stochastic (unbiased) rounding for ratio-1 uploads, per-tensor or block-wise, bits 1..8: a code is
+    # floor(t) or floor(t) + 1 with probability equal to the fraction, so the server's average of C uploads loses the
+    # round-to-nearest bias and its error falls as 1 / sqrt(C). Not on the wire: the server has no switch. A ratio
+    # below 1, bits 32 or codec_error_feedback next to it is a ValueError. codec_stochastic_seed: None draws 64 bits
+    # from os.urandom per client; an integer is folded with the client's cid. Off by default.
+    codec_stochastic = False
+    codec_stochastic_seed = None
 
     def reset_error_feedback(self):
         """Zero this client's residual (e.g. when it joins a new task with the same model)."""
@@ -274,12 +303,16 @@ class CompressionServerMixin(_CodecOwner):
     codec_download_blockwise = False  # block-wise download (wire v5): one min / scale pair per 4096-element block
                                       # instead of one per tensor, codes bit-packed; ratio 1, any bits <= 8; wins over
                                       # codec_download_pack
+    codec_download_stochastic = False  # stochastic (unbiased) rounding of the download's codes: ratio 1,
+                                       # bits 1..8, per-tensor or block-wise; the payload format does not change
+    codec_download_stochastic_seed = None  # its 64-bit seed (None: drawn from os.urandom once per server)
 
     def _download_codec(self):
         c = self.__dict__.get("_download_update_codec")
         if c is None:
             c = UpdateCodec(self.codec_download_ratio, self.codec_download_bits, "weights", self.codec_backend,
-                            pack_dense=self.codec_download_pack, blockwise=self.codec_download_blockwise)
+                            pack_dense=self.codec_download_pack, blockwise=self.codec_download_blockwise,
+                            stochastic=self.codec_download_stochastic, seed=self.codec_download_stochastic_seed)
             self.__dict__["_download_update_codec"] = c
         return c
 

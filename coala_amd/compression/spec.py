@@ -20,6 +20,21 @@ UNIT = 4096         # mirrors coalac.hip: elements per wave work unit
 VALID_BITS = tuple(range(1, 9)) + (RAW_BITS,)
 
 
+_M64 = (1 << 64) - 1
+
+
+def sr_call_seed(seed, n):
+    """The 64-bit seed of a codec's n-th stochastic encode: splitmix64's output function over
+    seed + (n + 1) * 0x9E3779B97F4A7C15 (mod 2^64). Also folds a client's identity into a configured seed
+    (n: a hash of its cid), so that two clients configured alike do not round alike."""
+    z = (int(seed) + (int(n) + 1) * 0x9E3779B97F4A7C15) & _M64
+    z ^= z >> 30
+    z = (z * 0xBF58476D1CE4E5B9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
 def small_limit(sizes):
     """The largest segment a plan over these segment sizes encodes whole in one block (coalac.hip
     coalac_plan_create): SMALL_MAX_LATENCY for latency-bound plans of <= LATENCY_PLAN_UNITS units, else

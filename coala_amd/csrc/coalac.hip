@@ -2969,6 +2969,95 @@ DEV void with_rcp(float mn, float scale, float levels, F&& f) {
     run(std::false_type{});
 }
 
+// Stochastic (unbiased) rounding of the dense quantisers, the one copy of its contract, host and
+// device: element c (its flat position, the segment's in_off + its index) of a call with the 64-bit `seed` draws 24
+// uniform bits from three rounds of the lowbias32 mixer — two over the seed and the high word of c (sr_key: the same
+// for every element of a unit that crosses no 2^32 boundary), one over the low word — and its code is floor(t) or
+// floor(t) + 1, the latter with probability t - floor(t) (exact in fp32; an integer t is kept).
+#define HOSTDEV __host__ __device__ __forceinline__
+HOSTDEV uint32_t sr_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+HOSTDEV uint32_t sr_key(uint64_t seed, uint32_t c_hi) {
+  return sr_mix(sr_mix(c_hi ^ (uint32_t)(seed >> 32) ^ 0x9E3779B9u) ^ (uint32_t)seed);
+}
+HOSTDEV uint32_t sr_u24_keyed(uint32_t key, uint32_t c_lo) { return sr_mix(c_lo ^ key) >> 8; }
+HOSTDEV uint32_t sr_u24(uint64_t seed, uint64_t c) { return sr_u24_keyed(sr_key(seed, (uint32_t)(c >> 32)), (uint32_t)c); }
+// t: the IEEE quotient (v - mn) / scale (the caller gives 0 where !(scale > 0)); u24: sr_u24's draw
+HOSTDEV uint32_t sr_code(float t, uint32_t u24, float levels) {
+  if (!(t > 0.0f)) return 0u;  // (NaN, v == mn)
+  if (t >= levels) return (uint32_t)levels;
+  const float f = floorf(t);
+  return (uint32_t)f + (((float)u24 * 0x1p-24f < t - f) ? 1u : 0u);
+}
+
+// with_rcp for a caller that rounds the quotient itself: f(tq) runs with tq(x) = the IEEE quotient (x - mn) / scale,
+// bit for bit, or 0 where !(scale > 0). The product form stands for the division only where tools/rcp_div_check.c
+// found them equal — scale in [2^-90, 2^90] and x - mn >= 2^-100 (or 0: both forms give 0); below that round-to-nearest
+// cannot tell them apart (both codes are 0) but a stochastic code can, so `proven` (dense_unit_proven, wave-uniform)
+// sends a unit that holds such a value to the division.
+template <class F>
+DEV void with_rcp_quotient(float mn, float scale, bool proven, F&& f) {
+  auto run = [&](auto rcp_tag) {
+    constexpr bool RCP = decltype(rcp_tag)::value;
+    const float y = RCP ? 1.0f / scale : 0.0f;
+    const bool pos = scale > 0.0f;
+    f([&](float x) -> float {
+      const float a = x - mn;
+      if (!RCP) return pos ? a / scale : 0.0f;
+      const float q = a * y;
+      return __builtin_fmaf(__builtin_fmaf(-q, scale, a), y, q);
+    });
+  };
+  if (dense_rcp_scale(scale) && proven)
+    run(std::true_type{});
+  else
+    run(std::false_type{});
+}
+
+// no value of the loaded unit has 0 < x - mn < 2^-100 (the bit pattern of x - mn, minus one, is below that of 2^-100
+// minus one exactly there: a negative or NaN difference has the high bits set); the same answer in every lane. The
+// positions past the unit's end hold 0.0f: they can only send the unit to the division, which is always right.
+DEV bool dense_unit_proven(const float4 (&v)[UNIT_IT], float mn) {
+  uint32_t m = 0xFFFFFFFFu;
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t b = __float_as_uint(xs[j] - mn) - 1u;
+      m = b < m ? b : m;
+    }
+  }
+  return __ballot(m < __float_as_uint(0x1p-100f) - 1u) == 0;
+}
+
+// A unit's stochastic-rounding key: sr_key of the high word of its first element's position c0 = in_off + start, from
+// the scalar unit when the unit's last element shares that word (wave-uniform), else `carry` tells each lane whether
+// its element's low word has wrapped (c_lo < c0's) and it takes the next word's key.
+struct SrUnit {
+  uint32_t lo, key, key1;
+  bool split;
+};
+DEV SrUnit sr_unit(uint64_t seed, uint64_t c0, uint32_t len) {
+  SrUnit s;
+  s.lo = (uint32_t)c0;
+  const uint32_t hi = (uint32_t)(c0 >> 32);
+  s.split = (uint32_t)((c0 + len - 1u) >> 32) != hi;
+  s.key = sr_key(seed, hi);
+  s.key1 = s.split ? sr_key(seed, hi + 1u) : s.key;
+  return s;
+}
+DEV uint32_t sr_draw(const SrUnit& s, uint32_t e) {
+  const uint32_t c = s.lo + e;
+  return sr_u24_keyed(s.split && c < s.lo ? s.key1 : s.key, c);
+}
+
 // the NaN-ignoring min / max of a loaded unit over the whole wave (every lane gets both)
 DEV void dense_unit_minmax(const float4 (&v)[UNIT_IT], uint32_t len, uint32_t lane, float& a, float& b) {
   a = qnan(), b = qnan();
@@ -3067,8 +3156,10 @@ __global__ __launch_bounds__(BLOCK) void k_dense_seg(Params P) {
 // SEGRED: every wave reduces its segment's per-unit min / max itself (k_dense_seg folded in: the unit's loads are in
 // flight meanwhile, the ~50 KB of pairs are L2-resident, and one launch boundary goes); the segment's first unit
 // writes its mn / scale. Used when every segment has a unit (an empty segment has no wave to write its zeros).
-template <bool DELTA, bool RAW, bool XCD, bool SEGRED>
-__global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
+// SR: stochastic rounding with the call's `seed`: the same loads, range and stores, each code from
+// sr_code of the IEEE quotient and the element's own draw (the integer hash is issued behind the unit's loads).
+template <bool DELTA, bool RAW, bool XCD, bool SEGRED, bool SR>
+DEV void dense_quant_unit(const Params& P, uint64_t seed) {
   const uint32_t u = (XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6);
   if (u >= P.n_units) return;
   const UnitDev U = P.units[u];
@@ -3130,18 +3221,43 @@ __global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
     const __amdgpu_buffer_rsrc_t r = bytes_rsrc(static_cast<uint8_t*>(P.vals) + o, U.len);
     // dense_code's reciprocal form: the IEEE division sequence it replaces cost 3.5 us of the download step
     // (profiles/r06_ab_dense_segred.txt)
-    with_rcp(mn, scale, P.levels, [&](auto qz) {
+    if constexpr (SR) {
+      const SrUnit sr = sr_unit(seed, U.off, U.len);
+      with_rcp_quotient(mn, scale, dense_rcp_scale(scale) && dense_unit_proven(v, mn), [&](auto tq) {
 #pragma unroll
-      for (uint32_t it = 0; it < UNIT_IT; ++it) {
-        const uint32_t c[4] = {qz(v[it].x), qz(v[it].y), qz(v[it].z), qz(v[it].w)};
-        dense_codes_store_row(r, vec, (it * 64 + lane) * 4, c);
-      }
-    });
+        for (uint32_t it = 0; it < UNIT_IT; ++it) {
+          const uint32_t e0 = (it * 64 + lane) * 4;
+          const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+          uint32_t c[4];
+#pragma unroll
+          for (uint32_t j = 0; j < 4; ++j) c[j] = sr_code(tq(xs[j]), sr_draw(sr, e0 + j), P.levels);
+          dense_codes_store_row(r, vec, e0, c);
+        }
+      });
+    } else {
+      with_rcp(mn, scale, P.levels, [&](auto qz) {
+#pragma unroll
+        for (uint32_t it = 0; it < UNIT_IT; ++it) {
+          const uint32_t c[4] = {qz(v[it].x), qz(v[it].y), qz(v[it].z), qz(v[it].w)};
+          dense_codes_store_row(r, vec, (it * 64 + lane) * 4, c);
+        }
+      });
+    }
   }
   if (P.idx != nullptr) {  // a caller that asked for the (implied) indices
     for (uint32_t e = lane; e < U.len; e += 64) P.idx[o + e] = (int32_t)(U.start + e);
   }
   if (P.ustart_out != nullptr && lane == 0) P.ustart_out[u] = U.start;
+}
+
+template <bool DELTA, bool RAW, bool XCD, bool SEGRED>
+__global__ __launch_bounds__(BLOCK) void k_dense_quant(Params P) {
+  dense_quant_unit<DELTA, RAW, XCD, SEGRED, false>(P, 0);
+}
+
+template <bool DELTA, bool XCD, bool SEGRED>
+__global__ __launch_bounds__(BLOCK) void k_dense_quant_sr(Params P, uint64_t seed) {
+  dense_quant_unit<DELTA, false, XCD, SEGRED, true>(P, seed);
 }
 
 // the decoded values of four uint8 codes in one dword (dense_codes_row)
@@ -3591,10 +3707,10 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq_stream(Params P, const uint
 // ceil(31 / 4 B) otherwise — and stores every word whole, consecutive lanes consecutive dwords. The stores are range-
 // checked to the unit's ceil(len B / 32) words, which lie inside its segment's [pw_s, pw_s + W_s).
 // ------------------------------------------------------------------------------------------------
-template <bool DELTA, uint32_t B, bool XCD>
-__global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uint64_t* __restrict__ pw,
-                                                             float* __restrict__ bmn, float* __restrict__ bscale,
-                                                             uint32_t* __restrict__ packed) {
+// SR: stochastic rounding, as dense_quant_unit's
+template <bool DELTA, uint32_t B, bool XCD, bool SR>
+DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw, float* __restrict__ bmn,
+                                float* __restrict__ bscale, uint32_t* __restrict__ packed, uint64_t seed) {
   constexpr uint32_t FB = 4u * B;                    // bits per field
   constexpr uint32_t NFIELD = UNIT / 4u;             // fields per unit (1024)
   constexpr bool ALIGNED = (32u % FB) == 0u;         // every word starts on a field (B = 1, 2, 4, 8)
@@ -3614,20 +3730,38 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uin
     bmn[u] = mn;
     bscale[u] = scale;
   }
-  with_rcp(mn, scale, P.levels, [&](auto qz) {
+  if constexpr (SR) {
+    const SrUnit sr = sr_unit(seed, U.off, len);
+    with_rcp_quotient(mn, scale, dense_rcp_scale(scale) && dense_unit_proven(v, mn), [&](auto tq) {
 #pragma unroll
-    for (uint32_t it = 0; it < UNIT_IT; ++it) {
-      const uint32_t e0 = (it * 64 + lane) * 4;
-      const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
-      uint32_t f = 0;
+      for (uint32_t it = 0; it < UNIT_IT; ++it) {
+        const uint32_t e0 = (it * 64 + lane) * 4;
+        const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+        uint32_t f = 0;
 #pragma unroll
-      for (uint32_t j = 0; j < 4; ++j) {
-        const uint32_t q = qz(xs[j]);
-        f |= ((len == UNIT || e0 + j < len) ? q : 0u) << (j * B);  // (a code past len is 0: the padding)
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t q = sr_code(tq(xs[j]), sr_draw(sr, e0 + j), P.levels);
+          f |= ((len == UNIT || e0 + j < len) ? q : 0u) << (j * B);  // (a code past len is 0: the padding)
+        }
+        fld[it * 64 + lane] = f;
       }
-      fld[it * 64 + lane] = f;
-    }
-  });
+    });
+  } else {
+    with_rcp(mn, scale, P.levels, [&](auto qz) {
+#pragma unroll
+      for (uint32_t it = 0; it < UNIT_IT; ++it) {
+        const uint32_t e0 = (it * 64 + lane) * 4;
+        const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+        uint32_t f = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t q = qz(xs[j]);
+          f |= ((len == UNIT || e0 + j < len) ? q : 0u) << (j * B);  // (a code past len is 0: the padding)
+        }
+        fld[it * 64 + lane] = f;
+      }
+    });
+  }
   lds_order();
   // (the offset and the resource apart, as k_aggregate_dense: through dense_unit_words_rsrc this kernel compiles to
   // another register allocation, which measured 2-3 % slower at B = 4)
@@ -3648,6 +3782,20 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uin
     }
     __builtin_amdgcn_raw_buffer_store_b32((uint32_t)acc, rout, (int)(w * 4u), 0, 0);  // (past the unit's words: dropped)
   }
+}
+
+template <bool DELTA, uint32_t B, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_block_quant(Params P, const uint64_t* __restrict__ pw,
+                                                             float* __restrict__ bmn, float* __restrict__ bscale,
+                                                             uint32_t* __restrict__ packed) {
+  dense_block_quant_unit<DELTA, B, XCD, false>(P, pw, bmn, bscale, packed, 0);
+}
+
+template <bool DELTA, uint32_t B, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_block_quant_sr(Params P, const uint64_t* __restrict__ pw,
+                                                                float* __restrict__ bmn, float* __restrict__ bscale,
+                                                                uint32_t* __restrict__ packed, uint64_t seed) {
+  dense_block_quant_unit<DELTA, B, XCD, true>(P, pw, bmn, bscale, packed, seed);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4009,6 +4157,20 @@ int launch_dense_encode(const Params& P, coalac_plan_t plan, hipStream_t st, con
   MARK(3);
   MARK(4);
   return COALAC_OK;
+}
+
+// the same sequence with the stochastic quantise stream (coalac_encode_sr: bits 1..8, no marks)
+template <bool DELTA>
+void launch_dense_encode_sr(const Params& P, coalac_plan_t plan, hipStream_t st, uint64_t seed) {
+  const dim3 g(ceil_div(P.n_units, WAVES));
+  const bool xcd = !plan->decode_latency;
+  with_flags([&](auto x) { hipLaunchKernelGGL((k_dense_minmax<DELTA, x.value>), g, dim3(BLOCK), 0, st, P); }, xcd);
+  if (plan->dense_empty) hipLaunchKernelGGL((k_dense_seg<false>), dim3(P.nseg), dim3(BLOCK), 0, st, P);
+  with_flags(
+      [&](auto x, auto segred) {
+        hipLaunchKernelGGL((k_dense_quant_sr<DELTA, x.value, segred.value>), g, dim3(BLOCK), 0, st, P, seed);
+      },
+      xcd, !plan->dense_empty);
 }
 
 // The sparse encode. By plan class (the file header lists the kernels):
@@ -4616,6 +4778,78 @@ int coalac_encode_block(coalac_plan_t plan, const float* d_in, const float* cons
       [&](auto b, auto delta, auto x) {
         launch_units(P, stream, k_dense_block_quant<delta.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
                      static_cast<uint32_t*>(d_packed));
+      },
+      d_base != nullptr, !plan->decode_latency);
+  return launched();
+}
+
+// the stochastic twins' own argument checks, every one of them ahead of the first device call
+static int sr_plan_args(coalac_plan_t plan, const char* who, const void* d_in, const void* d_seg_in) {
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if (!plan->dense)
+    return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); the sparse emit rounds to nearest", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to round", who);
+  if ((d_in != nullptr) == (d_seg_in != nullptr))
+    return fail(COALAC_EINVAL, "%s: exactly one of d_in and d_seg_in must be given", who);
+  return COALAC_OK;
+}
+
+int coalac_encode_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                     void* d_vals, float* d_mn, float* d_scale, void* d_ws, uint64_t ws_bytes, uint64_t seed,
+                     unsigned flags, void* stream) {
+  int rc = sr_plan_args(plan, "coalac_encode_sr", d_in, d_seg_in);
+  if (rc) return rc;
+  if (plan->proto.nseg == 0) return COALAC_OK;
+  if (!d_mn || !d_scale) return fail(COALAC_EINVAL, "coalac_encode_sr: mn/scale pointers are NULL");
+  if (plan->total_k && !d_vals) return fail(COALAC_EINVAL, "coalac_encode_sr: the vals pointer is NULL");
+  if (addr_bits(d_in, d_base) & 15) return fail(COALAC_EINVAL, "coalac_encode_sr: input/base must be 16-byte aligned");
+  if (!d_ws || ws_bytes < plan->ws_bytes)
+    return fail(COALAC_EWORKSPACE, "coalac_encode_sr: workspace %llu < required %llu", (unsigned long long)ws_bytes,
+                (unsigned long long)plan->ws_bytes);
+  rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.in = d_in;
+  P.inptr = d_seg_in;
+  P.base = d_base;
+  P.idx = nullptr;  // (implied, as the per-unit starts are)
+  P.vals = d_vals;
+  P.mn = d_mn;
+  P.scale = d_scale;
+  P.ustart_out = nullptr;
+  P.flags = flags;
+  carve_workspace(P, true, d_ws);
+  P.stamps = nullptr;
+  with_flags([&](auto delta) { launch_dense_encode_sr<delta.value>(P, plan, static_cast<hipStream_t>(stream), seed); },
+             d_base != nullptr);
+  return launched();
+}
+
+int coalac_encode_block_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                           float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t seed,
+                           void* stream) {
+  int rc = sr_plan_args(plan, "coalac_encode_block_sr", d_in, d_seg_in);
+  if (rc) return rc;
+  if (!d_bmn || !d_bscale || !d_packed) return fail(COALAC_EINVAL, "coalac_encode_block_sr: a pointer is NULL");
+  if (packed_bytes < 4 * plan->dense_words)
+    return fail(COALAC_EINVAL, "coalac_encode_block_sr: packed_bytes=%llu < the plan's %llu",
+                (unsigned long long)packed_bytes, (unsigned long long)(4 * plan->dense_words));
+  if (addr_bits(d_in, d_base) & 15)
+    return fail(COALAC_EINVAL, "coalac_encode_block_sr: input/base must be 16-byte aligned");
+  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
+    return fail(COALAC_EINVAL, "coalac_encode_block_sr: bmn / bscale / packed must be 4-byte aligned");
+  if (plan->proto.n_units == 0) return COALAC_OK;
+  rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.in = d_in;
+  P.inptr = d_seg_in;
+  P.base = d_base;
+  with_code_bits(
+      (uint32_t)plan->bits,
+      [&](auto b, auto delta, auto x) {
+        launch_units(P, stream, k_dense_block_quant_sr<delta.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
+                     static_cast<uint32_t*>(d_packed), seed);
       },
       d_base != nullptr, !plan->decode_latency);
   return launched();

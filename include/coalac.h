@@ -69,7 +69,10 @@ enum {
  * the one entry point coalac_aggregate_dense — the fused decode + FedAvg of ratio-1 uploads read from their own uint8
  * codes, wire v4 streams or block-wise (wire v5) streams; nothing that existed changes. ABI 11 adds the one entry point
  * coalac_aggregate_uploads — the sparse fused decode + FedAvg read from each upload's own idx / vals arrays or wire v3
- * stream; nothing that existed changes.) */
+ * stream; nothing that existed changes. Still ABI 11: the stochastic-rounding pair coalac_encode_sr /
+ * coalac_encode_block_sr is purely additive — two new symbols beside their deterministic twins, no existing entry
+ * point, flag, query, workspace size or payload changes — so the version a loader checks stays what it was; a caller
+ * that needs the pair looks the symbols up.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -233,6 +236,28 @@ int coalac_encode_block(coalac_plan_t plan, const float* d_in, const float* cons
                         float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, void* stream);
 int coalac_decode_block(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_bmn,
                         const float* d_bscale, const float* d_base, float* d_out, void* stream);
+
+/* Stochastic (unbiased) rounding for the dense quantisers. The range of every segment
+ * (coalac_encode_sr) or 4096-element unit (coalac_encode_block_sr) is computed exactly as by the deterministic twin;
+ * only the code of an element changes: with t = (v - mn) / scale (the IEEE fp32 quotient) it is floor(t) or
+ * floor(t) + 1, the latter when u < t - floor(t), where u in [0, 1) holds 24 bits hashed from `seed` and the element's
+ * flat position in_off_s + e (a pure function of the two: the same seed gives the same payload, with d_seg_in as with
+ * d_in). 0 where !(scale > 0) or !(t > 0), 2^bits - 1 where t >= it; an integer t is kept. The decoded value is an
+ * unbiased estimate of v, so the error of an average of C uploads encoded with different seeds falls as 1 / sqrt(C).
+ * The outputs are ordinary: coalac_decode*, coalac_pack_dense and coalac_aggregate_dense read them as they are.
+ *
+ * coalac_encode_sr is the dense encode of coalac_encode / coalac_encode_segptr: exactly one of d_in (flat fp32[span])
+ * and d_seg_in (a DEVICE array of per-segment pointers) is non-NULL, d_base != NULL selects delta mode, d_vals
+ * uint8[total_k], d_mn / d_scale fp32[nseg], the workspace is coalac_encode's; the indices and per-unit starts are
+ * implied and not written. coalac_encode_block_sr is coalac_encode_block plus the seed. Errors (COALAC_EINVAL): a
+ * sparse plan, bits == 32, both or neither input, and the NULL-pointer, size and alignment cases of the twins
+ * (COALAC_EWORKSPACE for a short workspace). A plan without segments (units) returns COALAC_OK and launches nothing. */
+int coalac_encode_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                     void* d_vals, float* d_mn, float* d_scale, void* d_ws, uint64_t ws_bytes, uint64_t seed,
+                     unsigned flags, void* stream);
+int coalac_encode_block_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                           float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t seed,
+                           void* stream);
 
 /* Profiling variants: identical work, plus hipEventRecord(events[i], stream) between kernels.
  * encode: [0] before k_sample, [1] after k_sample, [2] after k_scan, [3] after the select kernels
