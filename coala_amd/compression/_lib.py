@@ -70,6 +70,9 @@ SIGNATURES = [
     # seg pointers, base, bmn, bscale, packed, packed_bytes, seed, stream
     ("coalac_encode_sr", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _U64, _U64, ctypes.c_uint, _P]),
     ("coalac_encode_block_sr", _I, [_P, _P, _P, _P, _P, _P, _P, _U64, _U64, _P]),
+    # block-wise with error feedback in one pass: plan, in, seg pointers, base, resid, bmn, bscale, packed, packed_bytes,
+    # stream
+    ("coalac_encode_block_ef", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -89,7 +92,7 @@ SIGNATURES = [
 ABI_VERSION = 11
 # added without a version step (purely additive): a library of the same ABI version built before them (a COALAC_LIB
 # variant of an earlier commit) loads without them, and only a call that needs one fails
-ADDED_IN_ABI_11 = ("coalac_encode_sr", "coalac_encode_block_sr")
+ADDED_IN_ABI_11 = ("coalac_encode_sr", "coalac_encode_block_sr", "coalac_encode_block_ef")
 
 
 class CodecError(RuntimeError):

@@ -46,6 +46,12 @@ class HipBackend:
     def __init__(self):
         self._gather_ptrs = IdentityCache(16)  # keyed by value: the scalars' pointers -> the same on the device
 
+    @property
+    def block_error_feedback(self):
+        """Block-wise quantisation with error feedback: whether the loaded library exports
+        coalac_encode_block_ef (an ABI-11 build from before it loads without the symbol)."""
+        return hasattr(_lib.load(), "coalac_encode_block_ef")
+
     def default_device(self):
         return torch.device("cuda", torch.cuda.current_device())
 
@@ -371,7 +377,8 @@ class UpdateCodec:
                min / scale pair per 4096-element block instead of one per tensor, so a single large weight no longer
                sets the step of its whole tensor; the codes always travel bit-packed, and the encode is one pass over
                the update. Applies where pack_dense applies (and wins over it when both are set); below ratio 1 or at
-               bits 32 it is ignored. Not combinable with error feedback (residual=). Off by default.
+               bits 32 it is ignored. With error feedback (residual=) the encode is the fused one-pass form of
+               DESIGN.md §19 (plan.encode_block_ef; a backend without it: ValueError). Off by default.
         stochastic: ratio-1 (dense) updates with bits 1..8 — per-tensor or block-wise — are quantised with stochastic
                (unbiased) rounding: a code is floor(t) or floor(t) + 1 with probability equal to the
                fraction, so the decoded value is an unbiased estimate and the error of an average of C such updates
@@ -506,9 +513,11 @@ class UpdateCodec:
         plan = self.plan_for(L.sizes_key, device)
         blockwise = self.blockwise and self.ratio >= 1.0 and self.bits != RAW_BITS and _all_kept(plan)
         if blockwise:
-            if residual is not None:
-                raise ValueError("block-wise quantisation cannot be combined with error feedback (residual=): the "
-                                 "commit reads per-segment codes")
+            if residual is not None and (getattr(plan, "encode_block_ef", None) is None
+                                         or not getattr(plan, "has_block_ef", True)):
+                raise ValueError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
+                                 "has no encode_block_ef: block-wise quantisation cannot be combined with error "
+                                 "feedback (residual=) on it")
             if getattr(plan, "encode_block", None) is None:
                 raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
                                    "has no encode_block: block-wise quantisation is not available on it")
@@ -523,7 +532,9 @@ class UpdateCodec:
                                  f"has no {need}: stochastic rounding is not available on it")
             sr_seed = self._next_sr_seed()
         if residual is not None:
-            if getattr(plan, "ef_accumulate", None) is None or getattr(plan, "ef_commit", None) is None:
+            # (a block-wise plan's error feedback is its own one-pass encode, checked above)
+            if not blockwise and (getattr(plan, "ef_accumulate", None) is None
+                                  or getattr(plan, "ef_commit", None) is None):
                 raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
                                    "has no ef_accumulate / ef_commit: error feedback is not available on it")
             if residual.dtype != torch.float32 or residual.device != device or residual.dim() != 1 or \
@@ -551,7 +562,10 @@ class UpdateCodec:
                     self._checked_ptrs[id(plan)] = ptrs
         if blockwise:
             # wire v5: one pass — ranges per block, the bit-packed stream written directly (no workspace, no codes)
+            # (with a residual: the fused error feedback of DESIGN.md §19, still one launch and the same carrier)
             block, how = (plan.encode_block, {}) if sr_seed is None else (plan.encode_block_sr, {"seed": sr_seed})
+            if residual is not None:
+                block, how = plan.encode_block_ef, {"residual": residual}
             if in_place:
                 bmn, bscale, packed = block(tensors=segs, base=base_flat, stream=cur, checked=True, ptrs=ptrs, **how)
             else:

@@ -536,17 +536,38 @@ class CodecPlan:
         gives the same stream, and decode_block / aggregate_dense read it as any other."""
         return self._encode_block("encode_block_sr", seed, flat, tensors, base, out, stream, checked, ptrs)
 
-    def _sr_entry(self, name):
+    @property
+    def has_block_ef(self):
+        """Whether the loaded library exports coalac_encode_block_ef (an ABI-11 build from before it does not)."""
+        return hasattr(self._lib, "coalac_encode_block_ef")
+
+    def encode_block_ef(self, residual, flat=None, tensors=None, base=None, out=None, stream=None, checked=False,
+                        ptrs=None):
+        """encode_block with error feedback in the same pass (coalac_encode_block_ef): the unit
+        quantised is a = (x - base) + residual, and residual (fp32[span], this plan's flat layout, as ef_accumulate
+        takes it) leaves as a - decoded (+0.0 where that is not finite), rewritten in place; the padding between
+        segments is not written. Bit for bit ef_accumulate, encode_block(flat=residual) and the subtraction of
+        decode_block's output, in one launch. Returns encode_block's triple, an ordinary delta-mode wire v5 payload.
+        Asynchronous on `stream`."""
+        return self._encode_block("encode_block_ef", None, flat, tensors, base, out, stream, checked, ptrs,
+                                  resid=residual)
+
+    def _sr_entry(self, name, since="stochastic rounding"):
         fn = getattr(self._lib, name, None)
         if fn is None:
-            raise _lib.CodecError(f"the loaded codec library has no {name} (built before stochastic rounding)")
+            raise _lib.CodecError(f"the loaded codec library has no {name} (built before {since})")
         return fn
 
-    def _encode_block(self, who, seed, flat, tensors, base, out, stream, checked, ptrs):
-        # encode_block / encode_block_sr (seed None: the deterministic entry point)
+    def _encode_block(self, who, seed, flat, tensors, base, out, stream, checked, ptrs, resid=None):
+        # encode_block / encode_block_sr (seed None: the deterministic entry point) / encode_block_ef (resid given)
         self._need_dense(who)
         if (flat is None) == (tensors is None):
             raise ValueError(f"{who}: give exactly one of flat and tensors")
+        ef = who == "encode_block_ef"
+        if ef:
+            if resid is None:
+                raise ValueError("encode_block_ef: residual is None")
+            self._check_flat(resid, "residual")
         self._check_flat(base, "base")
         launch = torch.cuda.current_stream(self.device) if stream is None else stream
         if tensors is not None:
@@ -562,7 +583,11 @@ class CodecPlan:
         self._check_dense_packed(packed, "packed output")
         args = (self._h, x, seg, _ptr(base), _ptr(bmn), _ptr(bscale), _ptr(packed), ctypes.c_uint64(4 * packed.numel()))
         st = ctypes.c_void_p(launch.cuda_stream)
-        if seed is None:
+        if ef:
+            fn = self._sr_entry("coalac_encode_block_ef", since="the fused block-wise error feedback")
+            with _device_ctx(self.device):
+                rc = fn(*args[:4], _ptr(resid), *args[4:], st)
+        elif seed is None:
             with _device_ctx(self.device):
                 rc = self._lib.coalac_encode_block(*args, st)
         else:

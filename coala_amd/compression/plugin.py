@@ -38,7 +38,8 @@ Behaviour:
   * block-wise quantisation (opt-in, `codec_download_blockwise = True` on the server for the download, `codec_blockwise
     = True` on a client for a ratio-1 upload; any bits <= 8): one min / scale pair per 4096-element block instead of
     one per tensor, the codes bit-packed (wire v5). Self-describing; such uploads are decoded one by
-    one, not fused; not combinable with error feedback.
+    one, not fused. With `codec_error_feedback` the client's residual is updated in the same pass as the encode
+    (DESIGN.md §19), on a backend that has the fused encode (the HIP library; any other: ValueError).
   * stochastic rounding (opt-in, `codec_stochastic = True` on a client for a ratio-1 upload, `codec_download_stochastic =
     True` on the server for the download; bits 1..8, per-tensor or block-wise): unbiased codes, so the error of the
     server's average falls as 1 / sqrt(clients). The payload formats are unchanged; not combinable with
@@ -72,7 +73,7 @@ import zlib
 from torch import nn
 
 from . import wire
-from .codec import CompressedUpdate, UpdateCodec, _uniform
+from .codec import CompressedUpdate, HipBackend, UpdateCodec, _uniform
 from .download import CompressedModel, compress_model
 from .spec import sr_call_seed
 from .state import _layout_walk, _module_walk
@@ -116,11 +117,17 @@ class _CodecOwner:
     codec_recycle = True  # decoded modules are reused once released (UpdateCodec recycle; False: never)
 
     def _codec_blockwise(self):
-        """codec_blockwise, refused next to codec_error_feedback: the residual's commit reads per-segment codes."""
+        """codec_blockwise. Next to codec_error_feedback it needs a backend that declares the fused block-wise encode
+        with error feedback (`block_error_feedback`, DESIGN.md §19: the HIP backend when its library exports
+        coalac_encode_block_ef); the three-launch commit reads per-segment codes and cannot serve it."""
         on = bool(getattr(self, "codec_blockwise", False))
         if on and getattr(self, "codec_error_feedback", False):
-            raise ValueError("codec_blockwise cannot be combined with codec_error_feedback: the error-feedback commit "
-                             "reads per-segment codes, a block-wise payload has one range per 4096-element block")
+            backend = self.codec_backend if self.codec_backend is not None else HipBackend()
+            if not getattr(backend, "block_error_feedback", False):
+                raise ValueError("codec_blockwise cannot be combined with codec_error_feedback on the "
+                                 f"{getattr(backend, 'name', type(backend).__name__)!r} backend: it has no fused "
+                                 "block-wise encode with error feedback, and the error-feedback commit reads "
+                                 "per-segment codes, not one range per 4096-element block")
         return on
 
     def _codec_stochastic(self):
@@ -173,7 +180,8 @@ class CompressionClientMixin(_CodecOwner):
 
     # block-wise quantisation for ratio-1 uploads (wire v5): one min / scale pair per 4096-element block
     # instead of one per tensor, the codes always bit-packed. Applies where codec_pack_dense applies (bits 8 included)
-    # and wins over it; self-describing. Not combinable with codec_error_feedback (ValueError). Off by default.
+    # and wins over it; self-describing. With codec_error_feedback the residual is updated in the encode's own pass
+    #  where the backend has that encode (the HIP library), else ValueError. Off by default.
     codec_blockwise = False
 
     # stochastic (unbiased) rounding for ratio-1 uploads, per-tensor or block-wise, bits 1..8: a code is

@@ -3707,10 +3707,49 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq_stream(Params P, const uint
 // ceil(31 / 4 B) otherwise — and stores every word whole, consecutive lanes consecutive dwords. The stores are range-
 // checked to the unit's ceil(len B / 32) words, which lie inside its segment's [pw_s, pw_s + W_s).
 // ------------------------------------------------------------------------------------------------
-// SR: stochastic rounding, as dense_quant_unit's
-template <bool DELTA, uint32_t B, bool XCD, bool SR>
+// The fused error feedback's unit: v = (x - base) + r, k_ef_accumulate's arithmetic (fp32 subtract, then
+// fp32 add), EF_ROWS rows of each operand in flight as there. The operands are range-checked to the unit: a load past
+// its end gives 0. x and base are read once (non-temporal, as the quantise stream's); r is read with the default policy.
+constexpr int BLOCK_EF_STORE_AUX = 0;  // cache policy of the new residual's stores (0 plain, 2 non-temporal; A/B in
+                                       // DESIGN.md §19)
+template <bool HASBASE>
+DEV void ef_unit_load(const Params& P, const UnitDev& U, float4 (&v)[UNIT_IT]) {
+  static_assert(UNIT_IT % EF_ROWS == 0, "accumulate batch geometry");
+  typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+  const uint32_t lane = lane_id();
+  const float* xin = P.inptr != nullptr ? P.inptr[U.seg] + U.start : P.in + U.off;
+  const __amdgpu_buffer_rsrc_t rx = unit_rsrc(xin, U.len);
+  const __amdgpu_buffer_rsrc_t rb = unit_rsrc(HASBASE ? P.base + U.off : xin, U.len);
+  const __amdgpu_buffer_rsrc_t rr = unit_rsrc(P.out + U.off, U.len);
+#pragma unroll
+  for (uint32_t i0 = 0; i0 < UNIT_IT; i0 += EF_ROWS) {
+    u4v x[EF_ROWS], b[EF_ROWS], r[EF_ROWS];
+#pragma unroll
+    for (uint32_t it = 0; it < EF_ROWS; ++it) {
+      const int boff = (int)(((i0 + it) * 64 + lane) * 16);
+      x[it] = __builtin_amdgcn_raw_buffer_load_b128(rx, boff, 0, DENSE_Q_AUX);
+      if (HASBASE) b[it] = __builtin_amdgcn_raw_buffer_load_b128(rb, boff, 0, DENSE_Q_AUX);
+      r[it] = __builtin_amdgcn_raw_buffer_load_b128(rr, boff, 0, 0);
+    }
+#pragma unroll
+    for (uint32_t it = 0; it < EF_ROWS; ++it) {
+      float4 d = make_float4(__uint_as_float(x[it].x), __uint_as_float(x[it].y), __uint_as_float(x[it].z),
+                             __uint_as_float(x[it].w));
+      if (HASBASE)
+        d = make_float4(d.x - __uint_as_float(b[it].x), d.y - __uint_as_float(b[it].y), d.z - __uint_as_float(b[it].z),
+                        d.w - __uint_as_float(b[it].w));
+      v[i0 + it] = make_float4(d.x + __uint_as_float(r[it].x), d.y + __uint_as_float(r[it].y),
+                               d.z + __uint_as_float(r[it].z), d.w + __uint_as_float(r[it].w));
+    }
+  }
+}
+
+// SR: stochastic rounding, as dense_quant_unit's. EF: error feedback in the same pass:
+// the unit quantised is a = (x - base) + r, and r (P.out, laid out like the input) leaves as ef_residual(a, xhat).
+template <bool DELTA, uint32_t B, bool XCD, bool SR, bool EF = false>
 DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw, float* __restrict__ bmn,
                                 float* __restrict__ bscale, uint32_t* __restrict__ packed, uint64_t seed) {
+  static_assert(!(SR && EF), "stochastic rounding and error feedback are not combined (DESIGN.md §18)");
   constexpr uint32_t FB = 4u * B;                    // bits per field
   constexpr uint32_t NFIELD = UNIT / 4u;             // fields per unit (1024)
   constexpr bool ALIGNED = (32u % FB) == 0u;         // every word starts on a field (B = 1, 2, 4, 8)
@@ -3722,7 +3761,10 @@ DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw
   const uint32_t lane = lane_id(), len = U.len;
   uint32_t* fld = sfld[threadIdx.x >> 6];
   float4 v[UNIT_IT];
-  dense_unit_load<DELTA, DENSE_Q_AUX>(P, U, v);
+  if constexpr (EF)
+    ef_unit_load<DELTA>(P, U, v);
+  else
+    dense_unit_load<DELTA, DENSE_Q_AUX>(P, U, v);
   float a, b, mn, scale;
   dense_unit_minmax(v, len, lane, a, b);
   codec_range(a, b, P.levels, mn, scale);
@@ -3730,7 +3772,28 @@ DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw
     bmn[u] = mn;
     bscale[u] = scale;
   }
-  if constexpr (SR) {
+  if constexpr (EF) {
+    // (every load of r has returned: the range above is a reduction over all of v, so no store below can pass one)
+    const __amdgpu_buffer_rsrc_t rr = unit_rsrc(P.out + U.off, len);
+    with_rcp(mn, scale, P.levels, [&](auto qz) {
+#pragma unroll
+      for (uint32_t it = 0; it < UNIT_IT; ++it) {
+        const uint32_t e0 = (it * 64 + lane) * 4;
+        const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+        float rs[4];
+        uint32_t f = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t q = qz(xs[j]);
+          rs[j] = ef_residual(xs[j], dequantize((uint8_t)q, mn, scale));
+          f |= ((len == UNIT || e0 + j < len) ? q : 0u) << (j * B);  // (a code past len is 0: the padding)
+        }
+        fld[it * 64 + lane] = f;
+        // (a store past len is dropped: the padding between segments keeps what it held)
+        dense_store_row<BLOCK_EF_STORE_AUX>(rr, len, it, lane, make_float4(rs[0], rs[1], rs[2], rs[3]));
+      }
+    });
+  } else if constexpr (SR) {
     const SrUnit sr = sr_unit(seed, U.off, len);
     with_rcp_quotient(mn, scale, dense_rcp_scale(scale) && dense_unit_proven(v, mn), [&](auto tq) {
 #pragma unroll
@@ -3796,6 +3859,15 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant_sr(Params P, const 
                                                                 float* __restrict__ bmn, float* __restrict__ bscale,
                                                                 uint32_t* __restrict__ packed, uint64_t seed) {
   dense_block_quant_unit<DELTA, B, XCD, true>(P, pw, bmn, bscale, packed, seed);
+}
+
+// ... with error feedback in the same pass: r is read and rewritten in place, nothing else aliases it
+template <bool HASBASE, uint32_t B, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_block_quant_ef(Params P, const uint64_t* __restrict__ pw,
+                                                                float* __restrict__ bmn, float* __restrict__ bscale,
+                                                                uint32_t* __restrict__ packed, float* r) {
+  P.out = r;
+  dense_block_quant_unit<HASBASE, B, XCD, false, true>(P, pw, bmn, bscale, packed, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4850,6 +4922,44 @@ int coalac_encode_block_sr(coalac_plan_t plan, const float* d_in, const float* c
       [&](auto b, auto delta, auto x) {
         launch_units(P, stream, k_dense_block_quant_sr<delta.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
                      static_cast<uint32_t*>(d_packed), seed);
+      },
+      d_base != nullptr, !plan->decode_latency);
+  return launched();
+}
+
+int coalac_encode_block_ef(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                           float* d_resid, float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes,
+                           void* stream) {
+  // (every argument check comes before the first device call)
+  const char* who = "coalac_encode_block_ef";
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if ((d_in != nullptr) == (d_seg_in != nullptr))
+    return fail(COALAC_EINVAL, "%s: exactly one of d_in and d_seg_in must be given", who);
+  if (!d_resid) return fail(COALAC_EINVAL, "%s: residual pointer is NULL", who);
+  if (!d_bmn || !d_bscale || !d_packed) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  if (!plan->dense)
+    return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse plan's error feedback is "
+                "coalac_ef_accumulate / coalac_ef_commit", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
+  if (packed_bytes < 4 * plan->dense_words)
+    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
+                (unsigned long long)(4 * plan->dense_words));
+  if (addr_bits(d_in, d_base, d_resid) & 15)
+    return fail(COALAC_EINVAL, "%s: input/base/residual must be 16-byte aligned", who);
+  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
+    return fail(COALAC_EINVAL, "%s: bmn / bscale / packed must be 4-byte aligned", who);
+  if (plan->proto.n_units == 0) return COALAC_OK;
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.in = d_in;
+  P.inptr = d_seg_in;
+  P.base = d_base;
+  with_code_bits(
+      (uint32_t)plan->bits,
+      [&](auto b, auto hb, auto x) {
+        launch_units(P, stream, k_dense_block_quant_ef<hb.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
+                     static_cast<uint32_t*>(d_packed), d_resid);
       },
       d_base != nullptr, !plan->decode_latency);
   return launched();

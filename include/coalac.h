@@ -72,7 +72,8 @@ enum {
  * stream; nothing that existed changes. Still ABI 11: the stochastic-rounding pair coalac_encode_sr /
  * coalac_encode_block_sr is purely additive — two new symbols beside their deterministic twins, no existing entry
  * point, flag, query, workspace size or payload changes — so the version a loader checks stays what it was; a caller
- * that needs the pair looks the symbols up.) */
+ * that needs the pair looks the symbols up. The same holds for coalac_encode_block_ef, the block-wise encode with error
+ * feedback in one pass: one more symbol, nothing that existed changes.) */
 
 /* One fp32 segment (= one flattened tensor of the state_dict). Offsets are in ELEMENTS.
  *   in_off : start of the segment in the flat input / dense output buffer; must be a multiple of 4
@@ -257,6 +258,30 @@ int coalac_encode_sr(coalac_plan_t plan, const float* d_in, const float* const* 
                      unsigned flags, void* stream);
 int coalac_encode_block_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
                            float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t seed,
+                           void* stream);
+
+/* Error feedback for a block-wise upload in one pass (an addition to CodecSpec v1, bit for bit).
+ * coalac_encode_block of a = (x - base) + r with the residual r (d_resid: fp32[span], the plan's flat input layout,
+ * indexed by in_off, 16-byte aligned, zero at the start) read and rewritten in the same launch. Per 4096-element unit u:
+ *
+ *   a[i]      = (x[i] - base[i]) + r[i]        fp32 subtract, then fp32 add (d_base NULL: x[i] + r[i]) — exactly
+ *                                              coalac_ef_accumulate's arithmetic
+ *   bmn[u], bscale[u], code                    coalac_encode_block's, of the unit's a (a code past a ragged unit's end
+ *                                              is 0)
+ *   xhat      = bmn[u] + float(code) * bscale[u]   what coalac_decode_block writes without a base: fp32 multiply, then add
+ *   r[i]      = a[i] - xhat, stored as +0.0f where that is NaN or +-Inf (coalac_ef_commit's rule)
+ *
+ * Only the elements of segments are written to r: the padding between segments and everything past the last segment
+ * stay as they were. For any input, bmn, bscale, the stream and r equal the result of coalac_ef_accumulate(plan, x,
+ * base, r); coalac_encode_block(plan, d_in = r, no base); r[i] = r[i] - d[i] (+0.0f where not finite), d being
+ * coalac_decode_block of that payload without a base. The payload is an ordinary delta-mode wire v5 payload:
+ * coalac_decode_block and coalac_aggregate_dense (kind BLOCK) read it as any other. d_resid must not alias any other
+ * argument. One asynchronous launch on `stream`: no workspace, no allocation, no host synchronisation. COALAC_EINVAL
+ * (all checked before the first device call): every case coalac_encode_block rejects, d_resid NULL, d_resid not
+ * 16-byte aligned. A plan without units returns COALAC_OK and launches nothing. There is no stochastic variant
+ * (the residual already returns the rounding error to the client). */
+int coalac_encode_block_ef(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                           float* d_resid, float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes,
                            void* stream);
 
 /* Profiling variants: identical work, plus hipEventRecord(events[i], stream) between kernels.
