@@ -73,6 +73,12 @@ SIGNATURES = [
     # block-wise with error feedback in one pass: plan, in, seg pointers, base, resid, bmn, bscale, packed, packed_bytes,
     # stream
     ("coalac_encode_block_ef", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    # block sizes 256 / 1024 / 4096: plan, block, count / the block-wise twins' arguments with `block` behind the plan
+    # (the aggregate: behind clients, in the place of kind)
+    ("coalac_plan_block_count", _I, [_P, ctypes.c_uint32, ctypes.POINTER(_U64)]),
+    ("coalac_encode_block_g", _I, [_P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    ("coalac_decode_block_g", _I, [_P, ctypes.c_uint32, _P, _U64, _P, _P, _P, _P, _P]),
+    ("coalac_aggregate_dense_g", _I, [_P, _I, ctypes.c_uint32, _P, _U64, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -92,7 +98,9 @@ SIGNATURES = [
 ABI_VERSION = 11
 # added without a version step (purely additive): a library of the same ABI version built before them (a COALAC_LIB
 # variant of an earlier commit) loads without them, and only a call that needs one fails
-ADDED_IN_ABI_11 = ("coalac_encode_sr", "coalac_encode_block_sr", "coalac_encode_block_ef")
+ADDED_FOR_BLOCK_SIZES = ("coalac_plan_block_count", "coalac_encode_block_g", "coalac_decode_block_g",
+                         "coalac_aggregate_dense_g")
+ADDED_IN_ABI_11 = ("coalac_encode_sr", "coalac_encode_block_sr", "coalac_encode_block_ef") + ADDED_FOR_BLOCK_SIZES
 
 
 class CodecError(RuntimeError):

@@ -192,7 +192,8 @@ class CompressedUpdate:
             return wire.encode_header(dict(wh, entries=entries))
         # its JSON (with each raw entry's blob offset) depends on the layout and the raw byte counts only
         hjson = _PACKED_HEADERS.get(h["entries"], (self.signature, h["n_segments"], h.get("total_k"), h.get("n_units"),
-                                                   h.get("n_blocks"), tuple(map(len, rawb.values()))), header_json)
+                                                   h.get("n_blocks"), h.get("blockwise"),
+                                                   tuple(map(len, rawb.values()))), header_json)
         # ONE device-to-host copy, of the buffers the format ships (wire.section_list) and no other: where a packed
         # stream travels, idx and the uint8 codes stay where they are
         enc = self.encoded
@@ -379,6 +380,11 @@ class UpdateCodec:
                the update. Applies where pack_dense applies (and wins over it when both are set); below ratio 1 or at
                bits 32 it is ignored. With error feedback (residual=) the encode is the fused one-pass form of
                DESIGN.md §19 (plan.encode_block_ef; a backend without it: ValueError). Off by default.
+        block_size: the block size of blockwise: 4096 (the default), 1024 or 256 elements. A smaller
+               block isolates an outlier better — about 0.6x / 0.4x the RMS error of 4096 on heavy-tailed updates at 1024
+               / 256 — for 8 more bytes per block (+6 % of the payload at 4 bits and 256). The header names the size, so
+               a decoder and aggregate(..., dense_kernel=True) have no switch. Below 4096 the encode rounds to nearest
+               only: stochastic=True, a residual=, or a backend whose plan lacks encode_block_g is a ValueError.
         stochastic: ratio-1 (dense) updates with bits 1..8 — per-tensor or block-wise — are quantised with stochastic
                (unbiased) rounding: a code is floor(t) or floor(t) + 1 with probability equal to the
                fraction, so the decoded value is an unbiased estimate and the error of an average of C such updates
@@ -390,7 +396,7 @@ class UpdateCodec:
     """
 
     def __init__(self, ratio=0.01, bits=8, mode="delta", backend=None, recycle=True, compact=False, pack_dense=False,
-                 blockwise=False, stochastic=False, seed=None):
+                 blockwise=False, stochastic=False, seed=None, block_size=UNIT):
         if not (0.0 < float(ratio) <= 1.0):
             raise ValueError(f"ratio must be in (0, 1], got {ratio}")
         if bits not in VALID_BITS:
@@ -403,6 +409,10 @@ class UpdateCodec:
         self.pack_dense = bool(pack_dense)
         self.blockwise = bool(blockwise)
         self.stochastic = bool(stochastic)
+        self.block_size = wire.check_block_size(block_size)
+        if self.block_size != UNIT and self.stochastic:
+            raise ValueError(f"block_size {self.block_size} rounds to nearest only: stochastic rounding is defined for "
+                             f"{UNIT}-element blocks (DESIGN.md §20)")
         if self.stochastic:
             if self.ratio < 1.0:
                 raise ValueError(f"stochastic rounding covers the dense quantisers only (ratio 1), got ratio {ratio}: "
@@ -521,6 +531,11 @@ class UpdateCodec:
             if getattr(plan, "encode_block", None) is None:
                 raise RuntimeError(f"the {getattr(self.backend, 'name', type(self.backend).__name__)!r} backend's plan "
                                    "has no encode_block: block-wise quantisation is not available on it")
+            if self.block_size != UNIT:
+                if residual is not None:
+                    raise ValueError(f"block_size {self.block_size} cannot be combined with error feedback (residual=): "
+                                     f"the one-pass error feedback is defined for {UNIT}-element blocks (DESIGN.md §20)")
+                _block_methods(self.backend, plan, self.block_size, "block-wise quantisation")
         sr_seed = None
         if self.stochastic:
             if residual is not None:
@@ -566,12 +581,16 @@ class UpdateCodec:
             block, how = (plan.encode_block, {}) if sr_seed is None else (plan.encode_block_sr, {"seed": sr_seed})
             if residual is not None:
                 block, how = plan.encode_block_ef, {"residual": residual}
+            if self.block_size != UNIT:
+                block, how = plan.encode_block_g, {"block": self.block_size}
             if in_place:
                 bmn, bscale, packed = block(tensors=segs, base=base_flat, stream=cur, checked=True, ptrs=ptrs, **how)
             else:
                 bmn, bscale, packed = block(flat=flatten_state(state_fn(), device=device).flat, base=base_flat,
                                             stream=cur, **how)
-            header.update(total_k=int(plan.table.total_k), blockwise=UNIT, n_blocks=int(plan.table.n_units))
+            header.update(total_k=int(plan.table.total_k), blockwise=self.block_size,
+                          n_blocks=int(plan.table.n_units) if self.block_size == UNIT
+                          else wire.block_count(sizes, self.block_size))
             enc = Encoded(torch.empty(0, dtype=torch.int32, device=bmn.device), None, bmn, bscale, None, packed)
             return CompressedUpdate(header, enc, raw() if callable(raw) else raw, packed=packed)
         if residual is not None:
@@ -726,7 +745,7 @@ class UpdateCodec:
                 with torch.cuda.stream(side):
                     enc = update.encoded_to(device, staging=self._staging, plan=plan)
                     self._staged(side)
-                    flat = _decode_encoded(plan, fmt, enc, base_flat, out, side)
+                    flat = _decode_encoded(plan, fmt, enc, base_flat, out, side, block=_block_size(h))
                     if into is not None:
                         _copy_raw_groups(raw, into, non_blocking=True)
                 cur.wait_stream(side)
@@ -735,7 +754,8 @@ class UpdateCodec:
                     _reuse_after(into, None, None)
                 # (off the GPU only a block-wise update is read from its stream: a dense-packed one decodes from its codes)
                 enc = update.encoded_to(device) if fmt.per_block else update.encoded.to(device, non_blocking=True)
-                flat = _decode_encoded(plan, fmt, enc, base_flat, None if into is None else into.flat)
+                flat = _decode_encoded(plan, fmt, enc, base_flat, None if into is None else into.flat,
+                                       block=_block_size(h))
                 if into is not None:
                     _copy_raw_groups(raw, into)
         elif into is not None:
@@ -806,6 +826,11 @@ class UpdateCodec:
         if any(_dense_kind(u.header, e) != kind for u, e in zip(updates[1:], encs[1:])):
             raise ValueError("dense aggregation needs every upload in the same form on the device")
         codes = [e.vals if kind == "codes" else e.packed for e in encs]
+        block = _block_size(updates[0].header)
+        if kind == "block" and block != UNIT:  # (one block size per round: _uniform)
+            _block_methods(self.backend, plan, block, "the dense aggregate")
+            return plan.aggregate_dense_g(block, codes, [e.mn for e in encs], [e.scale for e in encs], weights,
+                                          total=total, base=base_flat, out=out, mode=mode, avg_mask=avg_mask)
         return plan.aggregate_dense(codes, [e.mn for e in encs], [e.scale for e in encs], weights, total=total,
                                     base=base_flat, out=out, mode=mode, avg_mask=avg_mask, kind=kind)
 
@@ -985,15 +1010,32 @@ def _dense_kind(header, enc):
 
 
 def _uniform(updates):
-    """Updates of one layout, ratio, bits, mode and payload format: what one fused aggregation takes."""
+    """Updates of one layout, ratio, bits, mode and payload format (block-wise ones: of one block size): what one fused
+    aggregation takes."""
     u0 = updates[0]
-    return all(u.signature == u0.signature and u.header["entries"] == u0.header["entries"] for u in updates[1:])
+    return all(u.signature == u0.signature and u.header["entries"] == u0.header["entries"]
+               and u.header.get("blockwise") == u0.header.get("blockwise") for u in updates[1:])
 
 
-def _decode_encoded(plan, fmt, enc, base, out, stream=None):
+def _block_size(header):
+    """The block size of a block-wise (wire v5) header, else UNIT."""
+    return int(header.get("blockwise", UNIT))
+
+
+def _block_methods(backend, plan, block, who):
+    """ValueError unless `plan` serves `block`-element blocks below 4096: the plan's encode_block_g /
+    decode_block_g / aggregate_dense_g, on a library that exports their entry points."""
+    if getattr(plan, "encode_block_g", None) is None or not getattr(plan, "has_block_g", True):
+        raise ValueError(f"the {getattr(backend, 'name', type(backend).__name__)!r} backend's plan has no "
+                         f"encode_block_g: {who} needs it for block size {block} (only {UNIT} is available on it)")
+
+
+def _decode_encoded(plan, fmt, enc, base, out, stream=None, block=UNIT):
     """The plan's decode of an update in the form encoded_to() left it in: a block-wise update from its stream with
-    each block's own range, a dense-packed one whose stream is on the device from the stream itself, else from its
-    idx / vals."""
+    each block's own range (block: its block size, the header's), a dense-packed one whose stream is on the device
+    from the stream itself, else from its idx / vals."""
+    if fmt.per_block and block != UNIT:
+        return plan.decode_block_g(block, enc.packed, enc.mn, enc.scale, base=base, out=out, stream=stream)
     if fmt.per_block:
         return plan.decode_block(enc.packed, enc.mn, enc.scale, base=base, out=out, stream=stream)
     if enc.packed is not None:

@@ -512,10 +512,11 @@ class CodecPlan:
                                    packed, mn, scale, base, out, stream)
 
     # -- block-wise dense quantisation (wire v5) --------------------------------------------------
-    def empty_block_encoded(self):
+    def empty_block_encoded(self, block=UNIT):
         """(bmn fp32[n_units], bscale fp32[n_units], packed uint32[dense_packed_words]) as views of ONE allocation
-        (16-byte aligned each): the outputs of encode_block."""
-        U, P = self.n_units, self.dense_packed_words
+        (16-byte aligned each): the outputs of encode_block; with another block size (encode_block_g) the ranges hold
+        block_count(block) entries."""
+        U, P = self.block_count(block), self.dense_packed_words
         a = (4 * U + 15) // 16 * 16
         buf = torch.empty(2 * a + 4 * P, dtype=torch.uint8, device=self.device)
         return (buf[:4 * U].view(torch.float32), buf[a:a + 4 * U].view(torch.float32),
@@ -558,8 +559,9 @@ class CodecPlan:
             raise _lib.CodecError(f"the loaded codec library has no {name} (built before {since})")
         return fn
 
-    def _encode_block(self, who, seed, flat, tensors, base, out, stream, checked, ptrs, resid=None):
-        # encode_block / encode_block_sr (seed None: the deterministic entry point) / encode_block_ef (resid given)
+    def _encode_block(self, who, seed, flat, tensors, base, out, stream, checked, ptrs, resid=None, block=UNIT):
+        # encode_block / encode_block_sr (seed None: the deterministic entry point) / encode_block_ef (resid given) /
+        # encode_block_g (block below 4096)
         self._need_dense(who)
         if (flat is None) == (tensors is None):
             raise ValueError(f"{who}: give exactly one of flat and tensors")
@@ -577,13 +579,16 @@ class CodecPlan:
             seg, x = _ptr(None), _ptr(flat)
         if out is None:
             with _on(stream):
-                out = self.empty_block_encoded()
+                out = self.empty_block_encoded(block)
         bmn, bscale, packed = out
-        self._check_ranges(who, self.n_units, "bmn / bscale", bmn, bscale)
+        self._check_ranges(who, self.block_count(block), "bmn / bscale", bmn, bscale)
         self._check_dense_packed(packed, "packed output")
         args = (self._h, x, seg, _ptr(base), _ptr(bmn), _ptr(bscale), _ptr(packed), ctypes.c_uint64(4 * packed.numel()))
         st = ctypes.c_void_p(launch.cuda_stream)
-        if ef:
+        if block != UNIT:
+            with _device_ctx(self.device):
+                rc = self._lib.coalac_encode_block_g(self._h, ctypes.c_uint32(block), *args[1:], st)
+        elif ef:
             fn = self._sr_entry("coalac_encode_block_ef", since="the fused block-wise error feedback")
             with _device_ctx(self.device):
                 rc = fn(*args[:4], _ptr(resid), *args[4:], st)
@@ -596,6 +601,69 @@ class CodecPlan:
                 rc = fn(*args, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), st)
         _lib.check(rc, "coalac_" + who)
         return bmn, bscale, packed
+
+    # -- block-wise with 256- and 1024-element blocks ------------------------------
+    BLOCK_SIZES = (256, 1024, UNIT)
+
+    @property
+    def has_block_g(self):
+        """Whether the loaded library exports the block-size entry points (an ABI-11 build from before them does not:
+        only block size 4096 works on it, through the entry points it has)."""
+        return all(hasattr(self._lib, n) for n in _lib.ADDED_FOR_BLOCK_SIZES)
+
+    def _block_size(self, who, block):
+        if isinstance(block, bool) or not isinstance(block, int) or block not in self.BLOCK_SIZES:
+            raise ValueError(f"{who}: block size {block!r}, need one of {self.BLOCK_SIZES}")
+        if block != UNIT and not self.has_block_g:
+            raise _lib.CodecError(f"{who}: the loaded codec library has no {_lib.ADDED_FOR_BLOCK_SIZES[1]} (built before "
+                                  f"block sizes other than {UNIT})")
+        return block
+
+    def block_count(self, block=UNIT):
+        """NB, the plan's number of `block`-element blocks: the sum over its segment rows of ceil(n / block)
+        (coalac_plan_block_count; wire.block_count of the rows' sizes). At 4096 it is n_units."""
+        self._need_dense("block_count")
+        if self._block_size("block_count", block) == UNIT:
+            return self.n_units
+        cache = self.__dict__.setdefault("_block_counts", {})
+        n = cache.get(block)
+        if n is None:
+            b = ctypes.c_uint64()
+            _lib.check(self._lib.coalac_plan_block_count(self._h, ctypes.c_uint32(block), ctypes.byref(b)),
+                       "coalac_plan_block_count")
+            n = cache[block] = b.value
+        return n
+
+    def encode_block_g(self, block, flat=None, tensors=None, base=None, out=None, stream=None, checked=False, ptrs=None):
+        """encode_block with `block`-element blocks (256, 1024 or 4096; coalac_encode_block_g): every block quantised over
+        its own range -> (bmn fp32[NB], bscale fp32[NB], packed uint32[dense_packed_words]), NB = block_count(block);
+        the stream's layout does not depend on the block size. Deterministic rounding only. At 4096 it is encode_block,
+        bit for bit. Asynchronous on `stream`."""
+        if self._block_size("encode_block_g", block) == UNIT:
+            return self.encode_block(flat, tensors, base, out, stream, checked, ptrs)
+        return self._encode_block("encode_block_g", None, flat, tensors, base, out, stream, checked, ptrs, block=block)
+
+    def decode_block_g(self, block, packed, bmn, bscale, base=None, out=None, stream=None):
+        """decode_block of a stream with `block`-element blocks (coalac_decode_block_g): bmn / bscale hold
+        block_count(block) entries. At 4096 it is decode_block, bit for bit. Asynchronous on `stream`."""
+        if self._block_size("decode_block_g", block) == UNIT:
+            return self.decode_block(packed, bmn, bscale, base, out, stream)
+        raw = self._lib.coalac_decode_block_g
+
+        def fn(h, *args):
+            return raw(h, ctypes.c_uint32(block), *args)
+        fn.__name__ = "coalac_decode_block_g"
+        return self._decode_stream(fn, "decode_block_g", self.block_count(block), "bmn / bscale", packed, bmn, bscale,
+                                   base, out, stream)
+
+    def aggregate_dense_g(self, block, codes, mns, scales, weights, total=None, base=None, out=None, mode="recip",
+                          avg_mask=None, stream=None):
+        """aggregate_dense, kind "block", of uploads with `block`-element blocks (coalac_aggregate_dense_g): every mn /
+        scale holds block_count(block) entries. At 4096 it is aggregate_dense(kind="block"), bit for bit."""
+        self._need_dense("aggregate_dense_g")
+        self._block_size("aggregate_dense_g", block)
+        return self.aggregate_dense(codes, mns, scales, weights, total, base, out, mode, avg_mask, "block", stream,
+                                    _block=block)
 
     def decode_block(self, packed, bmn, bscale, base=None, out=None, stream=None):
         """Decode of a block-wise stream (coalac_decode_block: decode_packed with each unit's own range) -> dense flat
@@ -719,7 +787,7 @@ class CodecPlan:
                        "block": _lib.COALAC_AGGD_BLOCK}
 
     def aggregate_dense(self, codes, mns, scales, weights, total=None, base=None, out=None, mode="recip",
-                        avg_mask=None, kind="codes", stream=None):
+                        avg_mask=None, kind="codes", stream=None, _block=UNIT):
         """Fused decode + FedAvg of C ratio-1 uploads of THIS plan's layout (a one-client dense plan), each read from
         its own buffers (coalac_aggregate_dense): no concatenation, no `clients`-copies plan, no implied
         indices. codes / mns / scales: lists of C tensors, one per upload —
@@ -743,7 +811,7 @@ class CodecPlan:
             raise ValueError(f"aggregate_dense: need one codes / mn / scale tensor and one weight per upload, got "
                              f"{C} / {len(mns)} / {len(scales)} / {len(weights)}")
         stream_kind = kind != "codes"
-        n_range = self.n_units if kind == "block" else self.n_segments
+        n_range = self.block_count(_block) if kind == "block" else self.n_segments  # (_block: aggregate_dense_g's)
         for i, (c, m, s) in enumerate(zip(codes, mns, scales)):
             if stream_kind:
                 self._check_dense_packed(c, f"upload {i}: packed stream")
@@ -775,11 +843,13 @@ class CodecPlan:
         total = float(sum(weights)) if total is None else float(total)
         code_bytes = min(c.numel() * c.element_size() for c in codes)
         p = ptrs.data_ptr()
+        rest = (ctypes.c_void_p(p), ctypes.c_uint64(code_bytes), ctypes.c_void_p(p + 8 * C), ctypes.c_void_p(p + 16 * C),
+                _ptr(w), ctypes.c_float(total), modes[mode], _ptr(m), _ptr(base), _ptr(out), _stream_handle(stream))
         with _device_ctx(self.device):
-            rc = self._lib.coalac_aggregate_dense(
-                self._h, C, self.AGG_DENSE_KINDS[kind], ctypes.c_void_p(p), ctypes.c_uint64(code_bytes),
-                ctypes.c_void_p(p + 8 * C), ctypes.c_void_p(p + 16 * C), _ptr(w), ctypes.c_float(total), modes[mode],
-                _ptr(m), _ptr(base), _ptr(out), _stream_handle(stream))
+            if _block != UNIT:
+                rc = self._lib.coalac_aggregate_dense_g(self._h, C, ctypes.c_uint32(_block), *rest)
+            else:
+                rc = self._lib.coalac_aggregate_dense(self._h, C, self.AGG_DENSE_KINDS[kind], *rest)
         _lib.check(rc, "coalac_aggregate_dense")
         return out  # ptrs / w / m were allocated on the launch stream: their memory is reused only after the kernel
 

@@ -75,7 +75,7 @@ from torch import nn
 from . import wire
 from .codec import CompressedUpdate, HipBackend, UpdateCodec, _uniform
 from .download import CompressedModel, compress_model
-from .spec import sr_call_seed
+from .spec import UNIT, sr_call_seed
 from .state import _layout_walk, _module_walk
 
 DATA_TYPE_FEATURE = 2  # coala/pb/common.proto: DataType.DATA_TYPE_FEATURE (protos/coala/pb/common.proto:26)
@@ -151,7 +151,8 @@ class _CodecOwner:
             c = UpdateCodec(self.codec_ratio, self.codec_bits, self.codec_mode, self.codec_backend,
                             recycle=self.codec_recycle, compact=getattr(self, "codec_compact", False),
                             pack_dense=getattr(self, "codec_pack_dense", False),
-                            blockwise=self._codec_blockwise(), stochastic=stochastic, seed=seed)
+                            blockwise=self._codec_blockwise(), stochastic=stochastic, seed=seed,
+                            block_size=getattr(self, "codec_block_size", UNIT))
             self.__dict__["_update_codec"] = c
         return c
 
@@ -183,6 +184,11 @@ class CompressionClientMixin(_CodecOwner):
     # and wins over it; self-describing. With codec_error_feedback the residual is updated in the encode's own pass
     #  where the backend has that encode (the HIP library), else ValueError. Off by default.
     codec_blockwise = False
+    # ... and its block size: 4096, 1024 or 256 elements. A smaller block follows an update's outliers
+    # more closely for 8 more bytes per block; the blob names its size, so the server has no switch. Below 4096 it cannot
+    # be combined with codec_stochastic or codec_error_feedback (ValueError). The reported upload size counts the longer
+    # range sections (CompressedUpdate.nbytes walks the header's own section list).
+    codec_block_size = UNIT
 
     # stochastic (unbiased) rounding for ratio-1 uploads, per-tensor or block-wise, bits 1..8: a code is
     # floor(t) or floor(t) + 1 with probability equal to the fraction, so the server's average of C uploads loses the
@@ -311,6 +317,7 @@ class CompressionServerMixin(_CodecOwner):
     codec_download_blockwise = False  # block-wise download (wire v5): one min / scale pair per 4096-element block
                                       # instead of one per tensor, codes bit-packed; ratio 1, any bits <= 8; wins over
                                       # codec_download_pack
+    codec_download_block_size = UNIT  # ... and its block size: 4096, 1024 or 256 elements
     codec_download_stochastic = False  # stochastic (unbiased) rounding of the download's codes: ratio 1,
                                        # bits 1..8, per-tensor or block-wise; the payload format does not change
     codec_download_stochastic_seed = None  # its 64-bit seed (None: drawn from os.urandom once per server)
@@ -320,7 +327,8 @@ class CompressionServerMixin(_CodecOwner):
         if c is None:
             c = UpdateCodec(self.codec_download_ratio, self.codec_download_bits, "weights", self.codec_backend,
                             pack_dense=self.codec_download_pack, blockwise=self.codec_download_blockwise,
-                            stochastic=self.codec_download_stochastic, seed=self.codec_download_stochastic_seed)
+                            stochastic=self.codec_download_stochastic, seed=self.codec_download_stochastic_seed,
+                            block_size=self.codec_download_block_size)
             self.__dict__["_download_update_codec"] = c
         return c
 

@@ -66,6 +66,10 @@ Version 5, BLOCK-WISE DENSE QUANTISATION (opt-in, "dense" updates with bits 1..8
     (also at bits 8, where it is simply the codes): the same W_s, pw_s, field order and zero padding, so a block starts
     at word pw_s + 128*b*u_s. The blob is 8 U + 4 P + raw payload bytes (plus header and alignment). unpack() returns
     mn / scale of length U and the rebuilt uint8 codes. block_count / block_table below are the block order on the host.
+    "blockwise" may also be 256 or 1024: the same format with blocks of G = that many elements —
+    ceil(n_s / G) blocks per segment, "n_blocks" their sum NB, block g_s of segment s covering its elements
+    [G g_s, min(n_s, G (g_s + 1))), mn / scale of length NB; the code stream does not change. A blob with
+    "blockwise": 4096 is byte for byte what it was before the other two sizes existed. No other size is defined.
 
 The executable form of the above is the table FORMATS below: one record per version with the version's ordered
 sections (name, dtype, element count) and its header rules. format_of(header) picks the record — nothing else in the
@@ -88,7 +92,8 @@ VERSION = 1     # mn | scale | idx | vals | raw
 VERSION_2 = 2   # ... | vals | ustart | raw
 VERSION_3 = 3   # mn | scale | packed | [vals f32] | ustart | raw  (header "compact": true)
 VERSION_4 = 4   # mn | scale | packed | raw  (header "dense": true, "dense_packed": true)
-VERSION_5 = 5   # mn[U] | scale[U] | packed | raw  (header "dense": true, "blockwise": 4096, "n_blocks": U)
+VERSION_5 = 5   # mn[U] | scale[U] | packed | raw  (header "dense": true, "blockwise": 256 | 1024 | 4096, "n_blocks": U)
+BLOCK_SIZES = (256, 1024, UNIT)  # the block sizes "blockwise" may name
 INDEX_BITS = 12  # low index bits in a packed field: log2(UNIT), the position inside the entry's 4096-element unit
 
 
@@ -255,18 +260,25 @@ def _seg_sizes(header):
     return _SIZES.get(header["entries"], (), _entry_sizes, header["entries"])
 
 
-def block_count(sizes):
-    """Blocks U of dense segments of `sizes` elements: the sum of ceil(n / 4096) (an empty segment has none)."""
+def check_block_size(block):
+    """`block` as an int if it is one of BLOCK_SIZES (a bool is not a size), else ValueError."""
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in BLOCK_SIZES:
+        raise ValueError(f"COALAQ1: block size {block!r} (only {', '.join(map(str, BLOCK_SIZES))} are defined)")
+    return int(block)
+
+
+def block_count(sizes, block=UNIT):
+    """Blocks U of dense segments of `sizes` elements: the sum of ceil(n / block) (an empty segment has none)."""
     n = np.asarray(sizes, dtype=np.int64).reshape(-1)
-    return int(((n + UNIT - 1) // UNIT).sum())
+    return int(((n + block - 1) // block).sum())
 
 
-def block_table(sizes):
-    """The block-wise format's view of dense segments laid out back to back: one row (offset, length) per block, in
-    block order — what a decoder applies mn[u] / scale[u] to. int64[U, 2]."""
+def block_table(sizes, block=UNIT):
+    """The block-wise format's view of dense segments laid out back to back: one row (offset, length) per block of
+    `block` elements, in block order — what a decoder applies mn[u] / scale[u] to. int64[U, 2]."""
     rows, off = [], 0
     for n in (int(x) for x in sizes):
-        rows += [(off + a, min(UNIT, n - a)) for a in range(0, n, UNIT)]
+        rows += [(off + a, min(block, n - a)) for a in range(0, n, block)]
         off += n
     return np.asarray(rows, dtype=np.int64).reshape(-1, 2)
 
@@ -335,12 +347,11 @@ def _v4_rules(h, dense, layout):
 def _v5_rules(h, dense, layout):
     if not dense:
         raise ValueError("COALAQ1: \"blockwise\" needs a \"dense\" payload")
-    if isinstance(h["blockwise"], bool) or int(h["blockwise"]) != UNIT:
-        raise ValueError(f"COALAQ1: block size {h['blockwise']!r} (only {UNIT} is defined)")
+    block = check_block_size(h["blockwise"])
     if h.get("dense_packed") or h.get("compact") or "n_units" in h:
         raise ValueError("COALAQ1: \"blockwise\" excludes \"dense_packed\", \"compact\" and per-unit starts")
     _need_code_bits(h, layout, 8, "block-wise")
-    if layout and int(h.get("n_blocks", -1)) != block_count(_seg_sizes(h)):
+    if layout and int(h.get("n_blocks", -1)) != block_count(_seg_sizes(h), block):
         raise ValueError("COALAQ1: header n_blocks is not the layout's block count")
 
 

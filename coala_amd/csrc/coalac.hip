@@ -3076,6 +3076,33 @@ DEV void dense_unit_minmax(const float4 (&v)[UNIT_IT], uint32_t len, uint32_t la
   b = wave_max(b);
 }
 
+// ... and of NR of its rows from row r0 on: a block of G = 256 NR elements below the unit. Rows past
+// the unit's end give NaN / NaN (no such block exists: its range is neither written nor read).
+template <uint32_t NR>
+DEV void dense_rows_minmax(const float4 (&v)[UNIT_IT], uint32_t r0, uint32_t len, uint32_t lane, float& a, float& b) {
+  a = qnan(), b = qnan();
+#pragma unroll
+  for (uint32_t it = r0; it < r0 + NR; ++it) {
+    const uint32_t e0 = (it * 64 + lane) * 4;
+    const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x = (len == UNIT || e0 + j < len) ? xs[j] : qnan();  // (loads past len read 0)
+      a = fmin_nan(a, x);
+      b = fmax_nan(b, x);
+    }
+  }
+  a = wave_min(a);
+  b = wave_max(b);
+}
+
+// The index of a unit's first G-element block in the range arrays: gb[s] blocks precede segment s
+// (the plan's table for G), UNIT / G of them every whole unit before this one. From the plan, never from a payload.
+template <uint32_t G>
+DEV uint64_t dense_block_index(const uint64_t* __restrict__ gb, const UnitDev& U) {
+  return gb[U.seg] + (uint64_t)(U.start >> UNIT_SHIFT) * (UNIT / G);
+}
+
 // A dense unit's codes sit at the positions themselves (k == n: entry e is element e): its first entry in vals, and
 // whether its codes can move as whole dwords — they start 4-byte aligned (16-byte for raw floats) and end on a dword.
 // The one copy: every kernel that reads or writes a unit's codes takes the same branch.
@@ -3694,6 +3721,45 @@ __global__ __launch_bounds__(BLOCK) void k_dense_deq_stream(Params P, const uint
   }
 }
 
+// k_dense_deq_stream for G-element blocks below the unit: a row takes the range of its block, at
+// dense_block_index (gb: the plan's block table for G) — UNIT / G wave-uniform pairs per unit, those of blocks past the
+// unit's end not read. A kernel of its own: the 4096 kernel above keeps its registers.
+template <uint32_t B, bool HASBASE, bool XCD, uint32_t G>
+__global__ __launch_bounds__(BLOCK) void k_dense_deq_stream_g(Params P, const uint64_t* __restrict__ pw,
+                                                              const uint64_t* __restrict__ gb,
+                                                              const uint32_t* __restrict__ packed,
+                                                              const float* __restrict__ rmn,
+                                                              const float* __restrict__ rscale) {
+  static_assert(G == 256u || G == 1024u, "blocks below the unit: 256 or 1024 elements");
+  constexpr uint32_t NBU = UNIT / G, RB = G / 256u;  // blocks per unit, rows per block
+  // (the unit as a scalar, as k_aggregate_dense's: the unit's record and its ranges are then scalar loads)
+  const uint32_t u =
+      __builtin_amdgcn_readfirstlane((XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6));
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id();
+  const uint64_t g0 = dense_block_index<G>(gb, U);
+  float mn[NBU], scale[NBU];
+#pragma unroll
+  for (uint32_t j = 0; j < NBU; ++j) {
+    const bool there = j * G < U.len;  // (wave-uniform; a block past the end: its rows are never stored)
+    mn[j] = there ? rmn[g0 + j] : 0.0f;
+    scale[j] = there ? rscale[g0 + j] : 0.0f;
+  }
+  const __amdgpu_buffer_rsrc_t rin = dense_unit_words_rsrc<B>(packed, pw, U);
+  uint32_t lo[UNIT_IT], hi[UNIT_IT];
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) dense_row_words<B>(rin, it, lane, lo[it], hi[it]);
+  const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
+  const __amdgpu_buffer_rsrc_t rb = unit_rsrc(HASBASE ? P.base + U.off : P.out + U.off, U.len);
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    float4 x = dense_row_values<B>(lo[it], hi[it], it, lane, mn[it / RB], scale[it / RB]);
+    if (HASBASE) x = dense_add_base(unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16), x);
+    dense_store_row(rout, U.len, it, lane, x);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // block-wise dense quantisation (wire v5): every 4096-element unit of a dense plan is quantised over its
 // OWN range — CodecSpec v1 applied to the unit as if it were a segment with k = n — and the codes leave as wire v4's
@@ -3746,10 +3812,15 @@ DEV void ef_unit_load(const Params& P, const UnitDev& U, float4 (&v)[UNIT_IT]) {
 
 // SR: stochastic rounding, as dense_quant_unit's. EF: error feedback in the same pass:
 // the unit quantised is a = (x - base) + r, and r (P.out, laid out like the input) leaves as ef_residual(a, xhat).
-template <bool DELTA, uint32_t B, bool XCD, bool SR, bool EF = false>
+// G: the block size: 4096, the unit itself, or 256 / 1024 — a block is then G / 256 of the unit's rows,
+// its range one wave reduction pair, written at dense_block_index (gb: the plan's block table for G).
+template <bool DELTA, uint32_t B, bool XCD, bool SR, bool EF = false, uint32_t G = UNIT>
 DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw, float* __restrict__ bmn,
-                                float* __restrict__ bscale, uint32_t* __restrict__ packed, uint64_t seed) {
+                                float* __restrict__ bscale, uint32_t* __restrict__ packed, uint64_t seed,
+                                const uint64_t* __restrict__ gb = nullptr) {
   static_assert(!(SR && EF), "stochastic rounding and error feedback are not combined (DESIGN.md §18)");
+  static_assert(G == UNIT || (!SR && !EF && (G == 256u || G == 1024u)),
+                "blocks below the unit: 256 or 1024 elements, deterministic only (DESIGN.md §20)");
   constexpr uint32_t FB = 4u * B;                    // bits per field
   constexpr uint32_t NFIELD = UNIT / 4u;             // fields per unit (1024)
   constexpr bool ALIGNED = (32u % FB) == 0u;         // every word starts on a field (B = 1, 2, 4, 8)
@@ -3766,13 +3837,41 @@ DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw
   else
     dense_unit_load<DELTA, DENSE_Q_AUX>(P, U, v);
   float a, b, mn, scale;
-  dense_unit_minmax(v, len, lane, a, b);
-  codec_range(a, b, P.levels, mn, scale);
-  if (lane == 0) {
-    bmn[u] = mn;
-    bscale[u] = scale;
+  if constexpr (G == UNIT) {
+    dense_unit_minmax(v, len, lane, a, b);
+    codec_range(a, b, P.levels, mn, scale);
+    if (lane == 0) {
+      bmn[u] = mn;
+      bscale[u] = scale;
+    }
   }
-  if constexpr (EF) {
+  if constexpr (G != UNIT) {
+    constexpr uint32_t RB = G / 256u;  // rows per block
+    const uint64_t g0 = dense_block_index<G>(gb, U);
+#pragma unroll
+    for (uint32_t j = 0; j < UNIT / G; ++j) {
+      dense_rows_minmax<RB>(v, j * RB, len, lane, a, b);
+      codec_range(a, b, P.levels, mn, scale);
+      if (lane == 0 && j * G < len) {  // (a block past the segment's end does not exist: no range is written)
+        bmn[g0 + j] = mn;
+        bscale[g0 + j] = scale;
+      }
+      with_rcp(mn, scale, P.levels, [&](auto qz) {
+#pragma unroll
+        for (uint32_t it = j * RB; it < (j + 1) * RB; ++it) {
+          const uint32_t e0 = (it * 64 + lane) * 4;
+          const float xs[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
+          uint32_t f = 0;
+#pragma unroll
+          for (uint32_t i = 0; i < 4; ++i) {
+            const uint32_t q = qz(xs[i]);
+            f |= ((len == UNIT || e0 + i < len) ? q : 0u) << (i * B);  // (a code past len is 0: the padding)
+          }
+          fld[it * 64 + lane] = f;
+        }
+      });
+    }
+  } else if constexpr (EF) {
     // (every load of r has returned: the range above is a reduction over all of v, so no store below can pass one)
     const __amdgpu_buffer_rsrc_t rr = unit_rsrc(P.out + U.off, len);
     with_rcp(mn, scale, P.levels, [&](auto qz) {
@@ -3859,6 +3958,14 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant_sr(Params P, const 
                                                                 float* __restrict__ bmn, float* __restrict__ bscale,
                                                                 uint32_t* __restrict__ packed, uint64_t seed) {
   dense_block_quant_unit<DELTA, B, XCD, true>(P, pw, bmn, bscale, packed, seed);
+}
+
+// ... with G-element blocks below the unit: gb is the plan's block table for G
+template <bool DELTA, uint32_t B, bool XCD, uint32_t G>
+__global__ __launch_bounds__(BLOCK) void k_dense_block_quant_g(Params P, const uint64_t* __restrict__ pw,
+                                                               const uint64_t* __restrict__ gb, float* __restrict__ bmn,
+                                                               float* __restrict__ bscale, uint32_t* __restrict__ packed) {
+  dense_block_quant_unit<DELTA, B, XCD, false, false, G>(P, pw, bmn, bscale, packed, 0, gb);
 }
 
 // ... with error feedback in the same pass: r is read and rewritten in place, nothing else aliases it
@@ -3966,6 +4073,91 @@ __global__ __launch_bounds__(BLOCK) void k_aggregate_dense(Params P, const uint6
       for (uint32_t it = 0; it < RI; ++it) {
         float4 x = KIND == COALAC_AGGD_CODES ? dense_codes_values(lo[t][it], mn[t], sc[t])
                                              : dense_row_values<B>(lo[t][it], hi[t][it], r0 + it, lane, mn[t], sc[t]);
+        if (HASBASE) x = dense_add_base(bv[it], x);
+        const float4 p = make_float4(x.x * w[t], x.y * w[t], x.z * w[t], x.w * w[t]);
+        acc[it] = make_float4(acc[it].x + p.x, acc[it].y + p.y, acc[it].z + p.z, acc[it].w + p.w);
+      }
+    }
+  }
+  auto store = [&](auto fin) {
+#pragma unroll
+    for (uint32_t it = 0; it < RI; ++it) dense_store_row(rout, U.len, r0 + it, lane, fin(acc[it]));
+  };
+  if (!avg || A.mode == COALAC_AGG_SUM)
+    store([&](float4 a) { return a; });
+  else if (A.mode == COALAC_AGG_DIV)
+    store([&](float4 a) { return agg_final<COALAC_AGG_DIV>(a, A.total, A.inv_total); });
+  else
+    store([&](float4 a) { return agg_final<COALAC_AGG_RECIP>(a, A.total, A.inv_total); });
+}
+
+// k_aggregate_dense, kind BLOCK, for G-element blocks below the unit: per client, the ranges of the
+// blocks this wave's rows lie in (NBW of them: one at G = 1024, four at G = 256), at dense_block_index (gb: the plan's
+// block table for G). The client order, the arithmetic and the stores are k_aggregate_dense's, statement for statement;
+// a kernel of its own, so that the 4096 kernel above keeps its registers.
+template <uint32_t B, bool HASBASE, uint32_t G>
+__global__ __launch_bounds__(BLOCK) void k_aggregate_dense_g(Params P, const uint64_t* __restrict__ pw,
+                                                             const uint64_t* __restrict__ gb, AggDenseArgs A) {
+  constexpr uint32_t RI = UNIT_IT / AGD_SPLIT, HE = UNIT / AGD_SPLIT, D = AGD_DEPTH;
+  static_assert(G == 256u || G == 1024u, "blocks below the unit: 256 or 1024 elements");
+  static_assert(G >= HE ? G % HE == 0 : HE % G == 0, "a wave's rows are whole blocks, or lie in one");
+  constexpr uint32_t NBW = G >= HE ? 1u : HE / G, RB = G / 256u;  // blocks per wave, rows per block
+  const uint32_t lane = lane_id();
+  const uint32_t wid = __builtin_amdgcn_readfirstlane((A.xcd ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6));
+  const uint32_t u = wid / AGD_SPLIT, r0 = (wid % AGD_SPLIT) * RI;  // the unit, and the first of this wave's rows
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  if (r0 * 256u >= U.len) return;
+  static_assert(HE == RI * 256u, "rows per wave");
+  const uint64_t ri = dense_block_index<G>(gb, U) + r0 / RB;  // the wave's first block
+  const bool avg = A.avg_mask == nullptr || A.avg_mask[U.seg] != 0;
+  const uint32_t ncl = avg ? A.clients : 1u;
+  uint32_t nwords = 0;
+  const uint64_t woff = dense_unit_word_off<B>(pw, U, nwords);
+  const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
+  float4 bv[RI], acc[RI];
+  if (HASBASE) {
+    const __amdgpu_buffer_rsrc_t rb = unit_rsrc(P.base + U.off, U.len);
+#pragma unroll
+    for (uint32_t it = 0; it < RI; ++it) bv[it] = unit_load_x4<false>(rb, rb, ((r0 + it) * 64 + lane) * 16);
+  }
+  // acc starts at -0.0f, the exact additive identity, so no client is special (as k_aggregate)
+#pragma unroll
+  for (uint32_t it = 0; it < RI; ++it) acc[it] = make_float4(-0.0f, -0.0f, -0.0f, -0.0f);
+  for (uint32_t c0 = 0; c0 < ncl; c0 += D) {
+    // round 1, wave-uniform: the clients' pointers, ranges and weights (a chunk's tail repeats the last client: every
+    // load stays inside some client's buffers, and the repeats are not accumulated)
+    const void* cp[D];
+    float mn[D][NBW], sc[D][NBW], w[D];
+#pragma unroll
+    for (uint32_t t = 0; t < D; ++t) {
+      const uint32_t c = min(c0 + t, ncl - 1);
+      cp[t] = A.codes[c];
+#pragma unroll
+      for (uint32_t j = 0; j < NBW; ++j) {
+        // (the wave's first block exists: r0 * 256 < len above; a later one past the end is not read, its rows not stored)
+        const bool there = j == 0 || (r0 + j * RB) * 256u < U.len;
+        mn[t][j] = there ? A.mn[c][ri + j] : 0.0f;
+        sc[t][j] = there ? A.scale[c][ri + j] : 0.0f;
+      }
+      w[t] = avg ? A.weights[c] : 1.0f;  // (x_0 * 1.0f == x_0)
+    }
+    // round 2: every code word of the chunk
+    uint32_t lo[D][RI], hi[D][RI];
+#pragma unroll
+    for (uint32_t t = 0; t < D; ++t) {
+      // (dense_unit_words_rsrc, the unit's offset shared by the clients' streams)
+      const __amdgpu_buffer_rsrc_t rin = bytes_rsrc(static_cast<const uint32_t*>(cp[t]) + woff, nwords * 4u);
+#pragma unroll
+      for (uint32_t it = 0; it < RI; ++it) dense_row_words<B>(rin, r0 + it, lane, lo[t][it], hi[t][it]);
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < D; ++t) {
+      if (c0 + t >= ncl) break;
+#pragma unroll
+      for (uint32_t it = 0; it < RI; ++it) {
+        const uint32_t j = NBW == 1 ? 0u : it / RB;  // the row's block among the wave's
+        float4 x = dense_row_values<B>(lo[t][it], hi[t][it], r0 + it, lane, mn[t][j], sc[t][j]);
         if (HASBASE) x = dense_add_base(bv[it], x);
         const float4 p = make_float4(x.x * w[t], x.y * w[t], x.z * w[t], x.w * w[t]);
         acc[it] = make_float4(acc[it].x + p.x, acc[it].y + p.y, acc[it].z + p.z, acc[it].w + p.w);
@@ -4131,6 +4323,9 @@ auto with_agg_mode(int mode, F&& f) {
 // the fork / join (~10-20 us) to pay off (>= 16384 large units, ~3 ResNet-50 updates).
 constexpr uint32_t FORK_MIN_LUNITS = 16384;
 
+// the block sizes below the unit, in the order of coalac_plan's n_blocks / dense_gb
+constexpr uint32_t SUB_BLOCKS[2] = {256u, 1024u};
+
 }  // namespace
 
 struct coalac_plan {
@@ -4153,6 +4348,10 @@ struct coalac_plan {
   // row's word offset in it (a device array inside meta)
   uint64_t dense_words = 0;
   const uint64_t* dense_pw = nullptr;
+  // ... and its blocks below the unit, for G = 256 [0] and G = 1024 [1]: the block count NB = sum of
+  // ceil(n_s / G), and each segment row's first block gb_s (a device array inside meta, behind dense_pw)
+  uint64_t n_blocks[2] = {0, 0};
+  const uint64_t* dense_gb[2] = {nullptr, nullptr};
   Params proto{};  // what every call's Params starts as: the metadata pointers (into meta), counts, levels and ccap
   void* meta = nullptr;
   std::vector<SegDev> hsegs;  // host copy (aggregate validates the client-copy structure)
@@ -4446,6 +4645,28 @@ int decode_stream(coalac_plan_t plan, bool per_unit, const void* d_packed, const
   return launched();
 }
 
+// the block size of a _g entry point: 4096 forwards to the twin (-1), 256 / 1024 give the plan's table index, anything
+// else is an error (-2)
+int sub_block_slot(uint32_t block) {
+  if (block == UNIT) return -1;
+  for (int i = 0; i < 2; ++i)
+    if (block == SUB_BLOCKS[i]) return i;
+  return -2;
+}
+
+int bad_block(const char* who, uint32_t block) {
+  return fail(COALAC_EINVAL, "%s: block=%u, need 256, 1024 or 4096", who, block);
+}
+
+// f(g) with the block size below the unit as a std::integral_constant<uint32_t, 256 | 1024>
+template <typename F>
+void with_sub_block(int slot, F&& f) {
+  if (slot == 0)
+    f(std::integral_constant<uint32_t, SUB_BLOCKS[0]>{});
+  else
+    f(std::integral_constant<uint32_t, SUB_BLOCKS[1]>{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -4564,17 +4785,22 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
   p->ws_bytes = carve_workspace(M, p->dense, nullptr);
   // a dense plan's bit-packed code stream (wire v4): each segment row's word offset, behind the tables in the plan's
   // one allocation (the stream's kernels take the array as an argument of their own: it is not in Params)
-  std::vector<uint64_t> dense_pw;
+  std::vector<uint64_t> dense_pw, dense_gb[2];
   if (p->dense && bits != 32) {
     dense_pw.reserve(T.segs.size());
     for (const SegDev& d : T.segs) {
       dense_pw.push_back(p->dense_words);
       p->dense_words += ((uint64_t)d.n * (uint64_t)bits + 31u) / 32u;
+      for (int i = 0; i < 2; ++i) {  // (the block tables of DESIGN.md §20, in the same row order)
+        dense_gb[i].push_back(p->n_blocks[i]);
+        p->n_blocks[i] += ceil_div(d.n, SUB_BLOCKS[i]);
+      }
     }
   }
 
   const size_t tables = place_tables(T, M, nullptr, nullptr);
-  const size_t bytes = tables + align_up(sizeof(uint64_t) * dense_pw.size(), 256);
+  const size_t pw_bytes = align_up(sizeof(uint64_t) * dense_pw.size(), 256);
+  const size_t bytes = tables + 3 * pw_bytes;
   std::vector<uint8_t> host(bytes, 0);
   hipError_t e = hipMalloc(&p->meta, bytes);
   if (e != hipSuccess) {
@@ -4585,6 +4811,11 @@ int coalac_plan_create(const coalac_seg_t* h_segs, int nseg, int bits, coalac_pl
   if (!dense_pw.empty()) {
     memcpy(host.data() + tables, dense_pw.data(), sizeof(uint64_t) * dense_pw.size());
     p->dense_pw = reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(p->meta) + tables);
+    for (int i = 0; i < 2; ++i) {
+      const size_t at = tables + (1 + i) * pw_bytes;
+      memcpy(host.data() + at, dense_gb[i].data(), sizeof(uint64_t) * dense_gb[i].size());
+      p->dense_gb[i] = reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(p->meta) + at);
+    }
   }
   e = hipMemcpy(p->meta, host.data(), bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -4976,6 +5207,89 @@ int coalac_decode_block(coalac_plan_t plan, const void* d_packed, uint64_t packe
   return decode_stream(plan, true, d_packed, d_bmn, d_bscale, d_base, d_out, stream);
 }
 
+int coalac_plan_block_count(coalac_plan_t plan, uint32_t block, uint64_t* n_blocks) {
+  const char* who = "coalac_plan_block_count";
+  if (!plan || !n_blocks) return fail(COALAC_EINVAL, "%s: plan or output pointer is NULL", who);
+  if (!plan->dense || plan->bits == 32)
+    return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n) with bits 1..8", who);
+  const int slot = sub_block_slot(block);
+  if (slot == -2) return bad_block(who, block);
+  *n_blocks = slot < 0 ? plan->proto.n_units : plan->n_blocks[slot];
+  return COALAC_OK;
+}
+
+int coalac_encode_block_g(coalac_plan_t plan, uint32_t block, const float* d_in, const float* const* d_seg_in,
+                          const float* d_base, float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes,
+                          void* stream) {
+  const char* who = "coalac_encode_block_g";
+  const int slot = sub_block_slot(block);
+  if (slot == -2) return bad_block(who, block);
+  if (slot < 0) return coalac_encode_block(plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed, packed_bytes, stream);
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if ((d_in != nullptr) == (d_seg_in != nullptr))
+    return fail(COALAC_EINVAL, "%s: exactly one of d_in and d_seg_in must be given", who);
+  if (!d_bmn || !d_bscale || !d_packed) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n)", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
+  if (packed_bytes < 4 * plan->dense_words)
+    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
+                (unsigned long long)(4 * plan->dense_words));
+  if (addr_bits(d_in, d_base) & 15) return fail(COALAC_EINVAL, "%s: input/base must be 16-byte aligned", who);
+  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
+    return fail(COALAC_EINVAL, "%s: bmn / bscale / packed must be 4-byte aligned", who);
+  if (plan->proto.n_units == 0) return COALAC_OK;
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.in = d_in;
+  P.inptr = d_seg_in;
+  P.base = d_base;
+  with_sub_block(slot, [&](auto g) {
+    with_code_bits(
+        (uint32_t)plan->bits,
+        [&](auto b, auto delta, auto x) {
+          launch_units(P, stream, k_dense_block_quant_g<delta.value, b.value, x.value, g.value>, plan->dense_pw,
+                       plan->dense_gb[slot], d_bmn, d_bscale, static_cast<uint32_t*>(d_packed));
+        },
+        d_base != nullptr, !plan->decode_latency);
+  });
+  return launched();
+}
+
+int coalac_decode_block_g(coalac_plan_t plan, uint32_t block, const void* d_packed, uint64_t packed_bytes,
+                          const float* d_bmn, const float* d_bscale, const float* d_base, float* d_out, void* stream) {
+  const char* who = "coalac_decode_block_g";
+  const int slot = sub_block_slot(block);
+  if (slot == -2) return bad_block(who, block);
+  if (slot < 0) return coalac_decode_block(plan, d_packed, packed_bytes, d_bmn, d_bscale, d_base, d_out, stream);
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if (!d_packed || !d_bmn || !d_bscale || !d_out) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n)", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
+  if (packed_bytes < 4 * plan->dense_words)
+    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
+                (unsigned long long)(4 * plan->dense_words));
+  if (addr_bits(d_packed, d_bmn, d_bscale) & 3)
+    return fail(COALAC_EINVAL, "%s: packed / bmn / bscale must be 4-byte aligned", who);
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "%s: output/base must be 16-byte aligned", who);
+  if (plan->proto.n_units == 0) return COALAC_OK;
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  with_sub_block(slot, [&](auto g) {
+    with_code_bits(
+        (uint32_t)plan->bits,
+        [&](auto b, auto h, auto x) {
+          launch_units(P, stream, k_dense_deq_stream_g<b.value, h.value, x.value, g.value>, plan->dense_pw,
+                       plan->dense_gb[slot], static_cast<const uint32_t*>(d_packed), d_bmn, d_bscale);
+        },
+        d_base != nullptr, !plan->decode_latency);
+  });
+  return launched();
+}
+
 int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, const void* d_vals,
                         const float* d_mn, const float* d_scale, const uint32_t* d_ustart, const float* d_weights,
                         float total, int mode,
@@ -5107,6 +5421,60 @@ int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void
     launch(std::integral_constant<int, COALAC_AGGD_PACKED>{});
   else
     launch(std::integral_constant<int, COALAC_AGGD_BLOCK>{});
+  return launched();
+}
+
+int coalac_aggregate_dense_g(coalac_plan_t plan, int clients, uint32_t block, const void* const* d_codes,
+                             uint64_t code_bytes, const float* const* d_mn, const float* const* d_scale,
+                             const float* d_weights, float total, int mode, const uint8_t* d_avg_mask,
+                             const float* d_base, float* d_out, void* stream) {
+  const char* who = "coalac_aggregate_dense_g";
+  const int slot = sub_block_slot(block);
+  if (slot == -2) return bad_block(who, block);
+  if (slot < 0)
+    return coalac_aggregate_dense(plan, clients, COALAC_AGGD_BLOCK, d_codes, code_bytes, d_mn, d_scale, d_weights, total,
+                                  mode, d_avg_mask, d_base, d_out, stream);
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse round is coalac_aggregate's", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to dequantise", who);
+  if (clients < 1) return fail(COALAC_EINVAL, "%s: clients=%d, need at least 1", who, clients);
+  if (mode != COALAC_AGG_DIV && mode != COALAC_AGG_RECIP && mode != COALAC_AGG_SUM)
+    return fail(COALAC_EINVAL, "%s: bad mode %d", who, mode);
+  if (!d_codes || !d_mn || !d_scale || !d_weights || !d_out) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  if (code_bytes < 4 * plan->dense_words)
+    return fail(COALAC_EINVAL, "%s: code_bytes=%llu < the plan's %llu", who, (unsigned long long)code_bytes,
+                (unsigned long long)(4 * plan->dense_words));
+  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "%s: output/base must be 16-byte aligned", who);
+  if (addr_bits(d_codes, d_mn, d_scale) & 7 || addr_bits(d_weights) & 3)
+    return fail(COALAC_EINVAL, "%s: the pointer arrays must be 8-byte, the weights 4-byte aligned", who);
+  if (plan->proto.n_units == 0) return COALAC_OK;
+  int rc = check_device(plan);
+  if (rc) return rc;
+  Params P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  AggDenseArgs A{};
+  A.codes = d_codes;
+  A.mn = d_mn;
+  A.scale = d_scale;
+  A.weights = d_weights;
+  A.avg_mask = d_avg_mask;
+  A.clients = (uint32_t)clients;
+  A.mode = mode;
+  A.xcd = !plan->decode_latency;
+  A.total = total;
+  A.inv_total = 1.0f / total;
+  const dim3 grid(ceil_div(P.n_units * (uint32_t)AGD_SPLIT, WAVES));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  with_sub_block(slot, [&](auto g) {
+    with_code_bits(
+        (uint32_t)plan->bits,
+        [&](auto b, auto hb) {
+          hipLaunchKernelGGL((k_aggregate_dense_g<b.value, hb.value, g.value>), grid, dim3(BLOCK), 0, st, P,
+                             plan->dense_pw, plan->dense_gb[slot], A);
+        },
+        d_base != nullptr);
+  });
   return launched();
 }
 

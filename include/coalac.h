@@ -362,6 +362,39 @@ int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void
                            const float* const* d_mn, const float* const* d_scale, const float* d_weights, float total,
                            int mode, const uint8_t* d_avg_mask, const float* d_base, float* d_out, void* stream);
 
+/* Block-wise dense quantisation with 256- and 1024-element blocks (an addition to CodecSpec v1, bit for
+ * bit). `block` is the block size G: 256, 1024 or 4096. With G = 4096 every entry point below gives its twin's result
+ * bit for bit (coalac_encode_block, coalac_decode_block, coalac_aggregate_dense with kind COALAC_AGGD_BLOCK). `plan` is a
+ * dense plan (every k == n), bits 1..8.
+ *
+ *   blocks       block g_s of segment s covers its elements [G g_s, min(n_s, G (g_s + 1))); blocks are numbered segment by
+ *                segment in the plan's row order, ceil(n_s / G) each (an empty segment has none): NB = sum of
+ *                ceil(n_s / G) — coalac_plan_block_count. The first block of segment s is gb_s = sum over t < s of
+ *                ceil(n_t / G); the block of row group j of the segment's 4096-element unit u_s is gb_s + u_s (4096 / G) + j
+ *   per block    exactly what coalac_encode_block does per unit: bmn the NaN-ignoring min + 0.0f, bscale CodecSpec v1's
+ *                range, the code the deterministic round-to-nearest code under the block's own range, a code past a
+ *                ragged block's end 0; decoded value bmn + float(code) * bscale (fp32 multiply, then add; + base)
+ *   code stream  wire v4's, unchanged in layout and length; d_bmn / d_bscale: fp32[NB] (not fp32[n_units])
+ *
+ * The ranges are indexed from the plan, never from the payload: a block that does not exist has no range written or
+ * read, and an untrusted stream can only mis-decode. coalac_encode_block_g is deterministic: there is no stochastic
+ * and no error-feedback variant below 4096. Arguments are the twins', plus `block`; each call is one asynchronous launch
+ * on `stream`: no allocation, no workspace, no host synchronisation. coalac_aggregate_dense_g is kind COALAC_AGGD_BLOCK
+ * with every d_mn[i] / d_scale[i] holding NB floats.
+ * COALAC_EINVAL (all checked before the first device call): every case the twin rejects, and a `block` other than 256,
+ * 1024 or 4096; coalac_plan_block_count: a NULL plan or output, a sparse plan, bits == 32, such a `block`. A plan without
+ * units returns COALAC_OK and launches nothing. */
+int coalac_plan_block_count(coalac_plan_t plan, uint32_t block, uint64_t* n_blocks);
+int coalac_encode_block_g(coalac_plan_t plan, uint32_t block, const float* d_in, const float* const* d_seg_in,
+                          const float* d_base, float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes,
+                          void* stream);
+int coalac_decode_block_g(coalac_plan_t plan, uint32_t block, const void* d_packed, uint64_t packed_bytes,
+                          const float* d_bmn, const float* d_bscale, const float* d_base, float* d_out, void* stream);
+int coalac_aggregate_dense_g(coalac_plan_t plan, int clients, uint32_t block, const void* const* d_codes,
+                             uint64_t code_bytes, const float* const* d_mn, const float* const* d_scale,
+                             const float* d_weights, float total, int mode, const uint8_t* d_avg_mask,
+                             const float* d_base, float* d_out, void* stream);
+
 /* coalac_aggregate from each SPARSE upload's own buffers. `plan` is a ONE-LAYOUT sparse plan (not dense;
  * bits 1..8 or 32): d_out / d_base are indexed by its in_off. The arithmetic is coalac_aggregate's contract bit for bit
  * (x_i = base + d_i, +0.0f where client i kept nothing; acc = x_0 * w_0, acc = acc + x_i * w_i in client order, no FMA;
