@@ -4598,16 +4598,53 @@ int packed_args(coalac_plan_t plan, const char* who, bool null_arg, uint64_t pac
   return *done ? COALAC_OK : check_device(plan);
 }
 
-// the dense stream's entry points: their shared checks (*done: nothing to launch), and the code width -> kernel
-int dense_packed_args(coalac_plan_t plan, const char* who, bool null_arg, uint64_t packed_bytes, bool* done) {
-  *done = false;
+// The dense stream's entry points (coalac_pack_dense, coalac_unpack_dense, coalac_decode_packed, coalac_encode_block*
+// and coalac_decode_block*): one description of a call's arguments and one walk over it, every
+// COALAC_EINVAL case ahead of the empty-plan return and of the first device call. A new entry point fills a DenseCall
+// and passes its launch as a lambda.
+constexpr const char* A_POINTER = "a pointer";
+constexpr const char* PACK_HINT = "; a sparse plan's payload is coalac_pack's";
+constexpr const char* SR_HINT = "; the sparse emit rounds to nearest";
+constexpr const char* EF_HINT = "; a sparse plan's error feedback is coalac_ef_accumulate / coalac_ef_commit";
+
+struct DenseCall {
+  const char* who;
+  const char* null_what;  // how the message names a required pointer that is NULL (nullptr: none is)
+  uint64_t packed_bytes;
+  uintptr_t a16;  // addr_bits of the pointers that must be 16-byte aligned, and what the message calls them
+  const char* names16;
+  uintptr_t a4;  // ... 4-byte aligned
+  const char* names4;
+  const char* hint = "";  // the end of "needs a dense plan": where the caller of a sparse plan should go
+  int inputs = 1;         // encoders: how many of d_in and d_seg_in were given
+};
+
+int input_count(const void* d_in, const void* d_seg_in) { return (d_in != nullptr) + (d_seg_in != nullptr); }
+
+int misaligned(const char* who, uintptr_t addrs, unsigned align, const char* names) {
+  if (addrs & (align - 1)) return fail(COALAC_EINVAL, "%s: %s must be %u-byte aligned", who, names, align);
+  return COALAC_OK;
+}
+
+// the plan's part (also coalac_encode_sr's, which has no stream): NULL, the inputs, the pointers, dense, a code width
+int dense_plan_args(coalac_plan_t plan, const char* who, int inputs, const char* null_what, const char* hint) {
   if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
-  if (null_arg) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
-  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse plan's payload is coalac_pack's", who);
-  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
-  if (packed_bytes < 4 * plan->dense_words)
-    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
+  if (inputs != 1) return fail(COALAC_EINVAL, "%s: exactly one of d_in and d_seg_in must be given", who);
+  if (null_what) return fail(COALAC_EINVAL, "%s: %s is NULL", who, null_what);
+  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n)%s", who, hint);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes (the fp32 values travel as they are)", who);
+  return COALAC_OK;
+}
+
+// *done: nothing to launch (a plan without units)
+int dense_stream_args(coalac_plan_t plan, const DenseCall& c, bool* done) {
+  *done = false;
+  int rc = dense_plan_args(plan, c.who, c.inputs, c.null_what, c.hint);
+  if (rc) return rc;
+  if (c.packed_bytes < 4 * plan->dense_words)
+    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", c.who, (unsigned long long)c.packed_bytes,
                 (unsigned long long)(4 * plan->dense_words));
+  if ((rc = misaligned(c.who, c.a16, 16, c.names16)) || (rc = misaligned(c.who, c.a4, 4, c.names4))) return rc;
   *done = plan->proto.n_units == 0;
   return *done ? COALAC_OK : check_device(plan);
 }
@@ -4626,23 +4663,6 @@ void with_code_bits(uint32_t b, F&& f, Flags... flags) {
 template <typename K, typename... Args>
 void launch_units(const Params& P, void* stream, K kernel, Args... args) {
   hipLaunchKernelGGL(kernel, dim3(ceil_div(P.n_units, WAVES)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), P, args...);
-}
-
-// coalac_decode_packed / coalac_decode_block behind their own checks: k_dense_deq_stream with one range per segment
-// or (per_unit) per unit
-int decode_stream(coalac_plan_t plan, bool per_unit, const void* d_packed, const float* d_mn, const float* d_scale,
-                  const float* d_base, float* d_out, void* stream) {
-  Params P = plan->proto;
-  P.base = d_base;
-  P.out = d_out;
-  with_code_bits(
-      (uint32_t)plan->bits,
-      [&](auto b, auto pu, auto h, auto x) {
-        launch_units(P, stream, k_dense_deq_stream<b.value, pu.value, h.value, x.value>, plan->dense_pw,
-                     static_cast<const uint32_t*>(d_packed), d_mn, d_scale);
-      },
-      per_unit, d_base != nullptr, !plan->decode_latency);
-  return launched();
 }
 
 // the block size of a _g entry point: 4096 forwards to the twin (-1), 256 / 1024 give the plan's table index, anything
@@ -4665,6 +4685,114 @@ void with_sub_block(int slot, F&& f) {
     f(std::integral_constant<uint32_t, SUB_BLOCKS[0]>{});
   else
     f(std::integral_constant<uint32_t, SUB_BLOCKS[1]>{});
+}
+
+// The block-wise encoders (coalac_encode_block, _sr, _ef, _g), checks and launch: the call's Params, then
+// k(P, b, delta, x) with the code width, delta mode and the XCD-aware order as constants — the entry point names its
+// kernel there and appends its own arguments. ef: d_resid is required too, and read and written 16 bytes at a time.
+template <typename K>
+int block_encode(const char* who, const char* hint, coalac_plan_t plan, const float* d_in, const float* const* d_seg_in,
+                 const float* d_base, float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, K&& k,
+                 bool ef = false, const float* d_resid = nullptr) {
+  const char* null_what = ef && !d_resid ? "residual pointer" : !d_bmn || !d_bscale || !d_packed ? A_POINTER : nullptr;
+  bool done = false;
+  int rc = dense_stream_args(plan, {who, null_what, packed_bytes, addr_bits(d_in, d_base, d_resid),
+                                    ef ? "input/base/residual" : "input/base", addr_bits(d_bmn, d_bscale, d_packed),
+                                    "bmn / bscale / packed", hint, input_count(d_in, d_seg_in)}, &done);
+  if (rc || done) return rc;
+  Params P = plan->proto;
+  P.in = d_in;
+  P.inptr = d_seg_in;
+  P.base = d_base;
+  with_code_bits((uint32_t)plan->bits, [&](auto b, auto delta, auto x) { k(P, b, delta, x); }, d_base != nullptr,
+                 !plan->decode_latency);
+  return launched();
+}
+
+// The stream decoders (coalac_decode_packed, coalac_decode_block, coalac_decode_block_g), checks and launch:
+// k_dense_deq_stream with one range per segment or (per_unit) per unit, or (slot >= 0) k_dense_deq_stream_g with one
+// per block of SUB_BLOCKS[slot] elements. The per-segment ranges are coalac_decode's: their alignment is not tested.
+int decode_stream(const char* who, coalac_plan_t plan, int slot, bool per_unit, const void* d_packed,
+                  uint64_t packed_bytes, const float* d_mn, const float* d_scale, const float* d_base, float* d_out,
+                  void* stream) {
+  const bool blocks = per_unit || slot >= 0;
+  bool done = false;
+  int rc = dense_stream_args(plan, {who, !d_packed || !d_mn || !d_scale || !d_out ? A_POINTER : nullptr, packed_bytes,
+                                    addr_bits(d_out, d_base), "output/base",
+                                    blocks ? addr_bits(d_packed, d_mn, d_scale) : addr_bits(d_packed),
+                                    blocks ? "packed / bmn / bscale" : "packed", PACK_HINT}, &done);
+  if (rc || done) return rc;
+  Params P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  const uint32_t bits = (uint32_t)plan->bits, *packed = static_cast<const uint32_t*>(d_packed);
+  const bool hb = d_base != nullptr, xcd = !plan->decode_latency;
+  if (slot < 0)
+    with_code_bits(
+        bits,
+        [&](auto b, auto pu, auto h, auto x) {
+          launch_units(P, stream, k_dense_deq_stream<b.value, pu.value, h.value, x.value>, plan->dense_pw, packed, d_mn,
+                       d_scale);
+        },
+        per_unit, hb, xcd);
+  else
+    with_sub_block(slot, [&](auto g) {
+      with_code_bits(
+          bits,
+          [&](auto b, auto h, auto x) {
+            launch_units(P, stream, k_dense_deq_stream_g<b.value, h.value, x.value, g.value>, plan->dense_pw,
+                         plan->dense_gb[slot], packed, d_mn, d_scale);
+          },
+          hb, xcd);
+    });
+  return launched();
+}
+
+// The dense aggregates' shared checks, every one ahead of the first device call (*done: nothing to launch). kind is
+// coalac_aggregate_dense's argument; the block sizes below the unit read the stream as COALAC_AGGD_BLOCK does.
+int agg_dense_args(const char* who, coalac_plan_t plan, int clients, int kind, int mode, const void* const* d_codes,
+                   uint64_t code_bytes, const float* const* d_mn, const float* const* d_scale, const float* d_weights,
+                   const float* d_base, float* d_out, bool* done) {
+  *done = false;
+  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
+  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse round is coalac_aggregate's", who);
+  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to dequantise", who);
+  if (clients < 1) return fail(COALAC_EINVAL, "%s: clients=%d, need at least 1", who, clients);
+  if (kind != COALAC_AGGD_CODES && kind != COALAC_AGGD_PACKED && kind != COALAC_AGGD_BLOCK)
+    return fail(COALAC_EINVAL, "%s: bad kind %d", who, kind);
+  if (mode != COALAC_AGG_DIV && mode != COALAC_AGG_RECIP && mode != COALAC_AGG_SUM)
+    return fail(COALAC_EINVAL, "%s: bad mode %d", who, mode);
+  if (!d_codes || !d_mn || !d_scale || !d_weights || !d_out) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
+  const uint64_t need = kind == COALAC_AGGD_CODES ? plan->total_k : 4 * plan->dense_words;
+  if (code_bytes < need)
+    return fail(COALAC_EINVAL, "%s: code_bytes=%llu < the plan's %llu", who, (unsigned long long)code_bytes,
+                (unsigned long long)need);
+  if (int rc = misaligned(who, addr_bits(d_out, d_base), 16, "output/base")) return rc;
+  if (addr_bits(d_codes, d_mn, d_scale) & 7 || addr_bits(d_weights) & 3)
+    return fail(COALAC_EINVAL, "%s: the pointer arrays must be 8-byte, the weights 4-byte aligned", who);
+  *done = plan->proto.n_units == 0;
+  return *done ? COALAC_OK : check_device(plan);
+}
+
+// ... and their launch operands: the call's Params and the kernels' AggDenseArgs; returns the grid
+dim3 agg_dense_setup(coalac_plan_t plan, int clients, const void* const* d_codes, const float* const* d_mn,
+                     const float* const* d_scale, const float* d_weights, float total, int mode,
+                     const uint8_t* d_avg_mask, const float* d_base, float* d_out, Params& P, AggDenseArgs& A) {
+  P = plan->proto;
+  P.base = d_base;
+  P.out = d_out;
+  A = AggDenseArgs{};
+  A.codes = d_codes;
+  A.mn = d_mn;
+  A.scale = d_scale;
+  A.weights = d_weights;
+  A.avg_mask = d_avg_mask;
+  A.clients = (uint32_t)clients;
+  A.mode = mode;
+  A.xcd = !plan->decode_latency;
+  A.total = total;
+  A.inv_total = 1.0f / total;
+  return dim3(ceil_div(P.n_units * (uint32_t)AGD_SPLIT, WAVES));
 }
 
 }  // namespace
@@ -5029,9 +5157,9 @@ int coalac_plan_dense_packed_bytes(coalac_plan_t plan, uint64_t* bytes) {
 
 int coalac_pack_dense(coalac_plan_t plan, const void* d_vals, void* d_packed, uint64_t packed_bytes, void* stream) {
   bool done = false;
-  int rc = dense_packed_args(plan, "coalac_pack_dense", !d_vals || !d_packed, packed_bytes, &done);
+  int rc = dense_stream_args(plan, {"coalac_pack_dense", !d_vals || !d_packed ? A_POINTER : nullptr, packed_bytes, 0, "",
+                                    addr_bits(d_packed, d_vals), "vals / packed", PACK_HINT}, &done);
   if (rc || done) return rc;
-  if (addr_bits(d_packed, d_vals) & 3) return fail(COALAC_EINVAL, "coalac_pack_dense: vals / packed must be 4-byte aligned");
   with_code_bits((uint32_t)plan->bits, [&](auto b) {
     launch_units(plan->proto, stream, k_pack_dense<b.value>, plan->dense_pw, static_cast<const uint8_t*>(d_vals),
                  static_cast<uint32_t*>(d_packed));
@@ -5041,9 +5169,9 @@ int coalac_pack_dense(coalac_plan_t plan, const void* d_vals, void* d_packed, ui
 
 int coalac_unpack_dense(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, void* d_vals, void* stream) {
   bool done = false;
-  int rc = dense_packed_args(plan, "coalac_unpack_dense", !d_packed || !d_vals, packed_bytes, &done);
+  int rc = dense_stream_args(plan, {"coalac_unpack_dense", !d_packed || !d_vals ? A_POINTER : nullptr, packed_bytes, 0, "",
+                                    addr_bits(d_packed, d_vals), "packed / vals", PACK_HINT}, &done);
   if (rc || done) return rc;
-  if (addr_bits(d_packed, d_vals) & 3) return fail(COALAC_EINVAL, "coalac_unpack_dense: packed / vals must be 4-byte aligned");
   with_code_bits((uint32_t)plan->bits, [&](auto b) {
     launch_units(plan->proto, stream, k_unpack_dense<b.value>, plan->dense_pw, static_cast<const uint32_t*>(d_packed),
                  static_cast<uint8_t*>(d_vals));
@@ -5053,59 +5181,28 @@ int coalac_unpack_dense(coalac_plan_t plan, const void* d_packed, uint64_t packe
 
 int coalac_decode_packed(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_mn,
                          const float* d_scale, const float* d_base, float* d_out, void* stream) {
-  bool done = false;
-  int rc = dense_packed_args(plan, "coalac_decode_packed", !d_packed || !d_mn || !d_scale || !d_out, packed_bytes, &done);
-  if (rc || done) return rc;
-  if (addr_bits(d_packed) & 3) return fail(COALAC_EINVAL, "coalac_decode_packed: packed must be 4-byte aligned");
-  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_decode_packed: output/base must be 16-byte aligned");
-  return decode_stream(plan, false, d_packed, d_mn, d_scale, d_base, d_out, stream);
+  return decode_stream("coalac_decode_packed", plan, -1, false, d_packed, packed_bytes, d_mn, d_scale, d_base, d_out, stream);
 }
 
 int coalac_encode_block(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
                         float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, void* stream) {
-  if (!plan) return fail(COALAC_EINVAL, "coalac_encode_block: plan is NULL");
-  if ((d_in != nullptr) == (d_seg_in != nullptr))
-    return fail(COALAC_EINVAL, "coalac_encode_block: exactly one of d_in and d_seg_in must be given");
-  bool done = false;
-  int rc = dense_packed_args(plan, "coalac_encode_block", !d_bmn || !d_bscale || !d_packed, packed_bytes, &done);
-  if (rc || done) return rc;
-  if (addr_bits(d_in, d_base) & 15) return fail(COALAC_EINVAL, "coalac_encode_block: input/base must be 16-byte aligned");
-  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
-    return fail(COALAC_EINVAL, "coalac_encode_block: bmn / bscale / packed must be 4-byte aligned");
-  Params P = plan->proto;
-  P.in = d_in;
-  P.inptr = d_seg_in;
-  P.base = d_base;
-  with_code_bits(
-      (uint32_t)plan->bits,
-      [&](auto b, auto delta, auto x) {
-        launch_units(P, stream, k_dense_block_quant<delta.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
-                     static_cast<uint32_t*>(d_packed));
-      },
-      d_base != nullptr, !plan->decode_latency);
-  return launched();
-}
-
-// the stochastic twins' own argument checks, every one of them ahead of the first device call
-static int sr_plan_args(coalac_plan_t plan, const char* who, const void* d_in, const void* d_seg_in) {
-  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
-  if (!plan->dense)
-    return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); the sparse emit rounds to nearest", who);
-  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to round", who);
-  if ((d_in != nullptr) == (d_seg_in != nullptr))
-    return fail(COALAC_EINVAL, "%s: exactly one of d_in and d_seg_in must be given", who);
-  return COALAC_OK;
+  return block_encode("coalac_encode_block", PACK_HINT, plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed, packed_bytes,
+                      [&](const Params& P, auto b, auto delta, auto x) {
+                        launch_units(P, stream, k_dense_block_quant<delta.value, b.value, x.value>, plan->dense_pw, d_bmn,
+                                     d_bscale, static_cast<uint32_t*>(d_packed));
+                      });
 }
 
 int coalac_encode_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
                      void* d_vals, float* d_mn, float* d_scale, void* d_ws, uint64_t ws_bytes, uint64_t seed,
                      unsigned flags, void* stream) {
-  int rc = sr_plan_args(plan, "coalac_encode_sr", d_in, d_seg_in);
+  // (no stream: the plan's part of the family's checks, then its own, every one ahead of the first device call)
+  int rc = dense_plan_args(plan, "coalac_encode_sr", input_count(d_in, d_seg_in), nullptr, SR_HINT);
   if (rc) return rc;
   if (plan->proto.nseg == 0) return COALAC_OK;
   if (!d_mn || !d_scale) return fail(COALAC_EINVAL, "coalac_encode_sr: mn/scale pointers are NULL");
   if (plan->total_k && !d_vals) return fail(COALAC_EINVAL, "coalac_encode_sr: the vals pointer is NULL");
-  if (addr_bits(d_in, d_base) & 15) return fail(COALAC_EINVAL, "coalac_encode_sr: input/base must be 16-byte aligned");
+  if ((rc = misaligned("coalac_encode_sr", addr_bits(d_in, d_base), 16, "input/base"))) return rc;
   if (!d_ws || ws_bytes < plan->ws_bytes)
     return fail(COALAC_EWORKSPACE, "coalac_encode_sr: workspace %llu < required %llu", (unsigned long long)ws_bytes,
                 (unsigned long long)plan->ws_bytes);
@@ -5131,80 +5228,28 @@ int coalac_encode_sr(coalac_plan_t plan, const float* d_in, const float* const* 
 int coalac_encode_block_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
                            float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t seed,
                            void* stream) {
-  int rc = sr_plan_args(plan, "coalac_encode_block_sr", d_in, d_seg_in);
-  if (rc) return rc;
-  if (!d_bmn || !d_bscale || !d_packed) return fail(COALAC_EINVAL, "coalac_encode_block_sr: a pointer is NULL");
-  if (packed_bytes < 4 * plan->dense_words)
-    return fail(COALAC_EINVAL, "coalac_encode_block_sr: packed_bytes=%llu < the plan's %llu",
-                (unsigned long long)packed_bytes, (unsigned long long)(4 * plan->dense_words));
-  if (addr_bits(d_in, d_base) & 15)
-    return fail(COALAC_EINVAL, "coalac_encode_block_sr: input/base must be 16-byte aligned");
-  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
-    return fail(COALAC_EINVAL, "coalac_encode_block_sr: bmn / bscale / packed must be 4-byte aligned");
-  if (plan->proto.n_units == 0) return COALAC_OK;
-  rc = check_device(plan);
-  if (rc) return rc;
-  Params P = plan->proto;
-  P.in = d_in;
-  P.inptr = d_seg_in;
-  P.base = d_base;
-  with_code_bits(
-      (uint32_t)plan->bits,
-      [&](auto b, auto delta, auto x) {
-        launch_units(P, stream, k_dense_block_quant_sr<delta.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
-                     static_cast<uint32_t*>(d_packed), seed);
-      },
-      d_base != nullptr, !plan->decode_latency);
-  return launched();
+  return block_encode("coalac_encode_block_sr", SR_HINT, plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed, packed_bytes,
+                      [&](const Params& P, auto b, auto delta, auto x) {
+                        launch_units(P, stream, k_dense_block_quant_sr<delta.value, b.value, x.value>, plan->dense_pw,
+                                     d_bmn, d_bscale, static_cast<uint32_t*>(d_packed), seed);
+                      });
 }
 
 int coalac_encode_block_ef(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
                            float* d_resid, float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes,
                            void* stream) {
-  // (every argument check comes before the first device call)
-  const char* who = "coalac_encode_block_ef";
-  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
-  if ((d_in != nullptr) == (d_seg_in != nullptr))
-    return fail(COALAC_EINVAL, "%s: exactly one of d_in and d_seg_in must be given", who);
-  if (!d_resid) return fail(COALAC_EINVAL, "%s: residual pointer is NULL", who);
-  if (!d_bmn || !d_bscale || !d_packed) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
-  if (!plan->dense)
-    return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse plan's error feedback is "
-                "coalac_ef_accumulate / coalac_ef_commit", who);
-  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
-  if (packed_bytes < 4 * plan->dense_words)
-    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
-                (unsigned long long)(4 * plan->dense_words));
-  if (addr_bits(d_in, d_base, d_resid) & 15)
-    return fail(COALAC_EINVAL, "%s: input/base/residual must be 16-byte aligned", who);
-  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
-    return fail(COALAC_EINVAL, "%s: bmn / bscale / packed must be 4-byte aligned", who);
-  if (plan->proto.n_units == 0) return COALAC_OK;
-  int rc = check_device(plan);
-  if (rc) return rc;
-  Params P = plan->proto;
-  P.in = d_in;
-  P.inptr = d_seg_in;
-  P.base = d_base;
-  with_code_bits(
-      (uint32_t)plan->bits,
-      [&](auto b, auto hb, auto x) {
+  return block_encode(
+      "coalac_encode_block_ef", EF_HINT, plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed, packed_bytes,
+      [&](const Params& P, auto b, auto hb, auto x) {
         launch_units(P, stream, k_dense_block_quant_ef<hb.value, b.value, x.value>, plan->dense_pw, d_bmn, d_bscale,
                      static_cast<uint32_t*>(d_packed), d_resid);
       },
-      d_base != nullptr, !plan->decode_latency);
-  return launched();
+      true, d_resid);
 }
 
 int coalac_decode_block(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_bmn,
                         const float* d_bscale, const float* d_base, float* d_out, void* stream) {
-  bool done = false;
-  int rc = dense_packed_args(plan, "coalac_decode_block", !d_packed || !d_bmn || !d_bscale || !d_out, packed_bytes, &done);
-  if (rc || done) return rc;
-  if (addr_bits(d_packed, d_bmn, d_bscale) & 3)
-    return fail(COALAC_EINVAL, "coalac_decode_block: packed / bmn / bscale must be 4-byte aligned");
-  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "coalac_decode_block: output/base must be 16-byte aligned");
-  return decode_stream(plan, true, d_packed, d_bmn, d_bscale, d_base, d_out, stream);
+  return decode_stream("coalac_decode_block", plan, -1, true, d_packed, packed_bytes, d_bmn, d_bscale, d_base, d_out, stream);
 }
 
 int coalac_plan_block_count(coalac_plan_t plan, uint32_t block, uint64_t* n_blocks) {
@@ -5225,35 +5270,15 @@ int coalac_encode_block_g(coalac_plan_t plan, uint32_t block, const float* d_in,
   const int slot = sub_block_slot(block);
   if (slot == -2) return bad_block(who, block);
   if (slot < 0) return coalac_encode_block(plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed, packed_bytes, stream);
-  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
-  if ((d_in != nullptr) == (d_seg_in != nullptr))
-    return fail(COALAC_EINVAL, "%s: exactly one of d_in and d_seg_in must be given", who);
-  if (!d_bmn || !d_bscale || !d_packed) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
-  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n)", who);
-  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
-  if (packed_bytes < 4 * plan->dense_words)
-    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
-                (unsigned long long)(4 * plan->dense_words));
-  if (addr_bits(d_in, d_base) & 15) return fail(COALAC_EINVAL, "%s: input/base must be 16-byte aligned", who);
-  if (addr_bits(d_bmn, d_bscale, d_packed) & 3)
-    return fail(COALAC_EINVAL, "%s: bmn / bscale / packed must be 4-byte aligned", who);
-  if (plan->proto.n_units == 0) return COALAC_OK;
-  int rc = check_device(plan);
-  if (rc) return rc;
-  Params P = plan->proto;
-  P.in = d_in;
-  P.inptr = d_seg_in;
-  P.base = d_base;
+  int rc = COALAC_OK;
   with_sub_block(slot, [&](auto g) {
-    with_code_bits(
-        (uint32_t)plan->bits,
-        [&](auto b, auto delta, auto x) {
-          launch_units(P, stream, k_dense_block_quant_g<delta.value, b.value, x.value, g.value>, plan->dense_pw,
-                       plan->dense_gb[slot], d_bmn, d_bscale, static_cast<uint32_t*>(d_packed));
-        },
-        d_base != nullptr, !plan->decode_latency);
+    rc = block_encode(who, PACK_HINT, plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed, packed_bytes,
+                      [&](const Params& P, auto b, auto delta, auto x) {
+                        launch_units(P, stream, k_dense_block_quant_g<delta.value, b.value, x.value, g.value>,
+                                     plan->dense_pw, plan->dense_gb[slot], d_bmn, d_bscale, static_cast<uint32_t*>(d_packed));
+                      });
   });
-  return launched();
+  return rc;
 }
 
 int coalac_decode_block_g(coalac_plan_t plan, uint32_t block, const void* d_packed, uint64_t packed_bytes,
@@ -5262,32 +5287,7 @@ int coalac_decode_block_g(coalac_plan_t plan, uint32_t block, const void* d_pack
   const int slot = sub_block_slot(block);
   if (slot == -2) return bad_block(who, block);
   if (slot < 0) return coalac_decode_block(plan, d_packed, packed_bytes, d_bmn, d_bscale, d_base, d_out, stream);
-  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
-  if (!d_packed || !d_bmn || !d_bscale || !d_out) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
-  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n)", who);
-  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to pack (the fp32 values travel as they are)", who);
-  if (packed_bytes < 4 * plan->dense_words)
-    return fail(COALAC_EINVAL, "%s: packed_bytes=%llu < the plan's %llu", who, (unsigned long long)packed_bytes,
-                (unsigned long long)(4 * plan->dense_words));
-  if (addr_bits(d_packed, d_bmn, d_bscale) & 3)
-    return fail(COALAC_EINVAL, "%s: packed / bmn / bscale must be 4-byte aligned", who);
-  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "%s: output/base must be 16-byte aligned", who);
-  if (plan->proto.n_units == 0) return COALAC_OK;
-  int rc = check_device(plan);
-  if (rc) return rc;
-  Params P = plan->proto;
-  P.base = d_base;
-  P.out = d_out;
-  with_sub_block(slot, [&](auto g) {
-    with_code_bits(
-        (uint32_t)plan->bits,
-        [&](auto b, auto h, auto x) {
-          launch_units(P, stream, k_dense_deq_stream_g<b.value, h.value, x.value, g.value>, plan->dense_pw,
-                       plan->dense_gb[slot], static_cast<const uint32_t*>(d_packed), d_bmn, d_bscale);
-        },
-        d_base != nullptr, !plan->decode_latency);
-  });
-  return launched();
+  return decode_stream(who, plan, slot, false, d_packed, packed_bytes, d_bmn, d_bscale, d_base, d_out, stream);
 }
 
 int coalac_aggregate_ev(coalac_plan_t plan, int clients, const int32_t* d_idx, const void* d_vals,
@@ -5366,44 +5366,17 @@ int coalac_aggregate(coalac_plan_t plan, int clients, const int32_t* d_idx, cons
 int coalac_aggregate_dense(coalac_plan_t plan, int clients, int kind, const void* const* d_codes, uint64_t code_bytes,
                            const float* const* d_mn, const float* const* d_scale, const float* d_weights, float total,
                            int mode, const uint8_t* d_avg_mask, const float* d_base, float* d_out, void* stream) {
-  const char* who = "coalac_aggregate_dense";
-  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
-  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse round is coalac_aggregate's", who);
-  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to dequantise", who);
-  if (clients < 1) return fail(COALAC_EINVAL, "%s: clients=%d, need at least 1", who, clients);
-  if (kind != COALAC_AGGD_CODES && kind != COALAC_AGGD_PACKED && kind != COALAC_AGGD_BLOCK)
-    return fail(COALAC_EINVAL, "%s: bad kind %d", who, kind);
-  if (mode != COALAC_AGG_DIV && mode != COALAC_AGG_RECIP && mode != COALAC_AGG_SUM)
-    return fail(COALAC_EINVAL, "%s: bad mode %d", who, mode);
-  if (!d_codes || !d_mn || !d_scale || !d_weights || !d_out) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
-  const uint64_t need = kind == COALAC_AGGD_CODES ? plan->total_k : 4 * plan->dense_words;
-  if (code_bytes < need)
-    return fail(COALAC_EINVAL, "%s: code_bytes=%llu < the plan's %llu", who, (unsigned long long)code_bytes,
-                (unsigned long long)need);
-  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "%s: output/base must be 16-byte aligned", who);
-  if (addr_bits(d_codes, d_mn, d_scale) & 7 || addr_bits(d_weights) & 3)
-    return fail(COALAC_EINVAL, "%s: the pointer arrays must be 8-byte, the weights 4-byte aligned", who);
-  if (plan->proto.n_units == 0) return COALAC_OK;
-  int rc = check_device(plan);
-  if (rc) return rc;
-  Params P = plan->proto;
-  P.base = d_base;
-  P.out = d_out;
-  AggDenseArgs A{};
-  A.codes = d_codes;
-  A.mn = d_mn;
-  A.scale = d_scale;
-  A.weights = d_weights;
-  A.avg_mask = d_avg_mask;
-  A.clients = (uint32_t)clients;
-  A.mode = mode;
-  A.xcd = !plan->decode_latency;
-  A.total = total;
-  A.inv_total = 1.0f / total;
-  const dim3 g(ceil_div(P.n_units * (uint32_t)AGD_SPLIT, WAVES));
+  bool done = false;
+  int rc = agg_dense_args("coalac_aggregate_dense", plan, clients, kind, mode, d_codes, code_bytes, d_mn, d_scale,
+                          d_weights, d_base, d_out, &done);
+  if (rc || done) return rc;
+  Params P;
+  AggDenseArgs A;
+  const dim3 g =
+      agg_dense_setup(plan, clients, d_codes, d_mn, d_scale, d_weights, total, mode, d_avg_mask, d_base, d_out, P, A);
   hipStream_t st = static_cast<hipStream_t>(stream);
   // One with_code_bits for the three kinds. CODES ignores the width it is handed: its codes are whole bytes, so all
-  // eight arms launch the same <8, CODES, hb>, and it relies on bits being in [1, 8] here (32 was rejected above) —
+  // eight arms launch the same <8, CODES, hb>, and it relies on bits being in [1, 8] here (agg_dense_args rejects 32) —
   // a width outside that range would launch nothing.
   auto launch = [&](auto k) {
     with_code_bits(
@@ -5434,37 +5407,14 @@ int coalac_aggregate_dense_g(coalac_plan_t plan, int clients, uint32_t block, co
   if (slot < 0)
     return coalac_aggregate_dense(plan, clients, COALAC_AGGD_BLOCK, d_codes, code_bytes, d_mn, d_scale, d_weights, total,
                                   mode, d_avg_mask, d_base, d_out, stream);
-  if (!plan) return fail(COALAC_EINVAL, "%s: plan is NULL", who);
-  if (!plan->dense) return fail(COALAC_EINVAL, "%s: needs a dense plan (every k == n); a sparse round is coalac_aggregate's", who);
-  if (plan->bits == 32) return fail(COALAC_EINVAL, "%s: bits == 32 has no codes to dequantise", who);
-  if (clients < 1) return fail(COALAC_EINVAL, "%s: clients=%d, need at least 1", who, clients);
-  if (mode != COALAC_AGG_DIV && mode != COALAC_AGG_RECIP && mode != COALAC_AGG_SUM)
-    return fail(COALAC_EINVAL, "%s: bad mode %d", who, mode);
-  if (!d_codes || !d_mn || !d_scale || !d_weights || !d_out) return fail(COALAC_EINVAL, "%s: a pointer is NULL", who);
-  if (code_bytes < 4 * plan->dense_words)
-    return fail(COALAC_EINVAL, "%s: code_bytes=%llu < the plan's %llu", who, (unsigned long long)code_bytes,
-                (unsigned long long)(4 * plan->dense_words));
-  if (addr_bits(d_out, d_base) & 15) return fail(COALAC_EINVAL, "%s: output/base must be 16-byte aligned", who);
-  if (addr_bits(d_codes, d_mn, d_scale) & 7 || addr_bits(d_weights) & 3)
-    return fail(COALAC_EINVAL, "%s: the pointer arrays must be 8-byte, the weights 4-byte aligned", who);
-  if (plan->proto.n_units == 0) return COALAC_OK;
-  int rc = check_device(plan);
-  if (rc) return rc;
-  Params P = plan->proto;
-  P.base = d_base;
-  P.out = d_out;
-  AggDenseArgs A{};
-  A.codes = d_codes;
-  A.mn = d_mn;
-  A.scale = d_scale;
-  A.weights = d_weights;
-  A.avg_mask = d_avg_mask;
-  A.clients = (uint32_t)clients;
-  A.mode = mode;
-  A.xcd = !plan->decode_latency;
-  A.total = total;
-  A.inv_total = 1.0f / total;
-  const dim3 grid(ceil_div(P.n_units * (uint32_t)AGD_SPLIT, WAVES));
+  bool done = false;
+  int rc = agg_dense_args(who, plan, clients, COALAC_AGGD_BLOCK, mode, d_codes, code_bytes, d_mn, d_scale, d_weights,
+                          d_base, d_out, &done);
+  if (rc || done) return rc;
+  Params P;
+  AggDenseArgs A;
+  const dim3 grid =
+      agg_dense_setup(plan, clients, d_codes, d_mn, d_scale, d_weights, total, mode, d_avg_mask, d_base, d_out, P, A);
   hipStream_t st = static_cast<hipStream_t>(stream);
   with_sub_block(slot, [&](auto g) {
     with_code_bits(

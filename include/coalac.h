@@ -205,7 +205,9 @@ int coalac_unpack(coalac_plan_t plan, const void* d_packed, uint64_t packed_byte
  * is a legal code, so an untrusted stream can mis-decode but not produce a code above 2^b - 1; padding bits are ignored.
  * Each call is one asynchronous launch on `stream`: no allocation, no workspace, no host synchronisation. Any NULL
  * pointer (d_base excepted), a sparse plan, a plan with bits == 32, or a packed_bytes below
- * coalac_plan_dense_packed_bytes (= 4 P) is COALAC_EINVAL; d_packed and d_vals are 4-byte aligned. */
+ * coalac_plan_dense_packed_bytes (= 4 P) is COALAC_EINVAL; d_packed and d_vals are 4-byte aligned. Here and in the
+ * block-wise entry points below every COALAC_EINVAL case is checked before the first device call, and before a plan
+ * without units returns COALAC_OK. */
 int coalac_plan_dense_packed_bytes(coalac_plan_t plan, uint64_t* bytes);
 int coalac_pack_dense(coalac_plan_t plan, const void* d_vals, void* d_packed, uint64_t packed_bytes, void* stream);
 int coalac_unpack_dense(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, void* d_vals, void* stream);

@@ -4,25 +4,11 @@
 // linked: struct coalac_plan lives in it.
 #include "../coala_amd/csrc/coalac.hip"
 
-static int g_failures = 0;
-#define CHECK(cond)                                                     \
-  do {                                                                  \
-    if (!(cond)) {                                                      \
-      printf("FAILED %s:%d: %s [%s]\n", __FILE__, __LINE__, #cond, coalac_last_error()); \
-      ++g_failures;                                                     \
-    }                                                                   \
-  } while (0)
-
-static bool says(const char* part) { return strstr(coalac_last_error(), part) != nullptr; }
+#include "host_check_common.h"
 
 static void argument_checks() {
-  coalac_plan dense, sparse, raw;  // (in host memory: every check below returns before the first device call)
-  for (coalac_plan* p : {&dense, &sparse, &raw}) {
-    p->dense = true, p->bits = 4, p->proto.nseg = 1, p->proto.n_units = 1, p->total_k = 64, p->span = 64;
-    p->ws_bytes = 256, p->dense_words = 8;
-  }
-  sparse.dense = false;
-  raw.bits = 32;
+  HostPlans p;
+  coalac_plan &dense = p.dense, &sparse = p.sparse, &raw = p.raw;
   alignas(16) static float x[64];
   alignas(16) static float res[64];
   alignas(16) static uint32_t out[64];
@@ -55,8 +41,9 @@ static void argument_checks() {
   CHECK(coalac_encode_block_ef(&dense, x, N, x, res + 2, r, r, out, 32, N) == COALAC_EINVAL && says("16-byte"));
   CHECK(coalac_encode_block_ef(&dense, N, &seg, N, res + 3, r, r, out, 32, N) == COALAC_EINVAL && says("16-byte"));
   // the checks are the same for a plan without units ...
-  dense.proto.nseg = 0, dense.proto.n_units = 0;
+  p.empty_dense();
   CHECK(coalac_encode_block_ef(&dense, x, N, N, N, r, r, out, 32, N) == COALAC_EINVAL && says("residual pointer is NULL"));
+  CHECK(coalac_encode_block_ef(&dense, x, N, N, res + 1, r, r, out, 32, N) == COALAC_EINVAL && says("16-byte"));
   // ... which otherwise is OK and launches nothing (a launch on this host-memory plan would fail)
   CHECK(coalac_encode_block_ef(&dense, x, N, N, res, r, r, out, 32, N) == COALAC_OK);
   CHECK(coalac_encode_block_ef(&dense, N, &seg, x, res, r, r, out, 32, N) == COALAC_OK);
@@ -65,6 +52,5 @@ static void argument_checks() {
 
 int main() {
   argument_checks();
-  printf(g_failures ? "block ef host checks: %d FAILED\n" : "block ef host checks: ok\n", g_failures);
-  return g_failures ? 1 : 0;
+  return report("block ef host checks");
 }

@@ -1,22 +1,14 @@
 // Host-side checks of coalac.hip that need no device, meant to be built with the host sanitizers
 // (tests/test_host_sanitized.py builds and runs it): every plan-validation error, the NULL-argument cases of every
-// entry point, and the workspace / plan-table walks against independently stated sizes — with real host buffers of
+// entry point, every argument check of coalac_pack_dense / coalac_unpack_dense / coalac_decode_packed (on plans in host
+// memory), and the workspace / plan-table walks against independently stated sizes — with real host buffers of
 // exactly the walked size, every array written end to end, so an array the walk sized too small is an overrun the
 // sanitizer reports. The codec source is included, not linked: the walks live in its anonymous namespace.
 #include "../coala_amd/csrc/coalac.hip"
 
 #include <cinttypes>
 
-static int g_failures = 0;
-#define CHECK(cond)                                                     \
-  do {                                                                  \
-    if (!(cond)) {                                                      \
-      printf("FAILED %s:%d: %s [%s]\n", __FILE__, __LINE__, #cond, coalac_last_error()); \
-      ++g_failures;                                                     \
-    }                                                                   \
-  } while (0)
-
-static bool says(const char* part) { return strstr(coalac_last_error(), part) != nullptr; }
+#include "host_check_common.h"
 
 static void plan_validation() {
   struct Row {
@@ -77,6 +69,55 @@ static void null_arguments() {
   CHECK(coalac_gather(&src, 1, 8, reinterpret_cast<uint8_t*>(&stamp) + 4, N) == COALAC_EINVAL && says("not aligned"));
   CHECK(coalac_gather(N, 0, 4, N, N) == COALAC_OK);
   CHECK(coalac_version() == COALAC_ABI_VERSION);
+}
+
+// coalac_pack_dense, coalac_unpack_dense and coalac_decode_packed: every COALAC_EINVAL case, each ahead of the empty
+// plan's COALAC_OK and of the first device call, on plans in host memory
+static void dense_stream() {
+  HostPlans p;
+  alignas(16) static float x[64];
+  alignas(16) static uint32_t out[64];
+  const auto N = nullptr;
+  float* r = reinterpret_cast<float*>(out);
+  uint8_t* bytes = reinterpret_cast<uint8_t*>(out);
+  for (int empty = 0; empty < 2; ++empty) {  // (the second time on a plan without units: the same answers)
+    if (empty) p.empty_dense();
+    // coalac_pack_dense(plan, vals, packed, packed_bytes, stream) / coalac_unpack_dense(plan, packed, packed_bytes, vals, stream)
+    CHECK(coalac_pack_dense(N, x, out, 32, N) == COALAC_EINVAL && says("coalac_pack_dense: plan is NULL"));
+    CHECK(coalac_pack_dense(&p.dense, N, out, 32, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_pack_dense(&p.dense, x, N, 32, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_pack_dense(&p.sparse, x, out, 32, N) == COALAC_EINVAL && says("dense plan") && says("coalac_pack's"));
+    CHECK(coalac_pack_dense(&p.raw, x, out, 32, N) == COALAC_EINVAL && says("bits == 32"));
+    CHECK(coalac_pack_dense(&p.dense, x, out, 28, N) == COALAC_EINVAL && says("packed_bytes"));
+    CHECK(coalac_pack_dense(&p.dense, bytes + 2, x, 32, N) == COALAC_EINVAL && says("4-byte"));
+    CHECK(coalac_pack_dense(&p.dense, x, bytes + 1, 32, N) == COALAC_EINVAL && says("4-byte"));
+    CHECK(coalac_unpack_dense(N, out, 32, x, N) == COALAC_EINVAL && says("coalac_unpack_dense: plan is NULL"));
+    CHECK(coalac_unpack_dense(&p.dense, N, 32, x, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_unpack_dense(&p.dense, out, 32, N, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_unpack_dense(&p.sparse, out, 32, x, N) == COALAC_EINVAL && says("dense plan"));
+    CHECK(coalac_unpack_dense(&p.raw, out, 32, x, N) == COALAC_EINVAL && says("bits == 32"));
+    CHECK(coalac_unpack_dense(&p.dense, out, 28, x, N) == COALAC_EINVAL && says("packed_bytes"));
+    CHECK(coalac_unpack_dense(&p.dense, bytes + 2, 32, x, N) == COALAC_EINVAL && says("4-byte"));
+    CHECK(coalac_unpack_dense(&p.dense, out, 32, bytes + 3, N) == COALAC_EINVAL && says("4-byte"));
+    // coalac_decode_packed(plan, packed, packed_bytes, mn, scale, base, out, stream)
+    CHECK(coalac_decode_packed(N, out, 32, r, r, N, x, N) == COALAC_EINVAL && says("coalac_decode_packed: plan is NULL"));
+    CHECK(coalac_decode_packed(&p.dense, N, 32, r, r, N, x, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_decode_packed(&p.dense, out, 32, N, r, N, x, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_decode_packed(&p.dense, out, 32, r, N, N, x, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_decode_packed(&p.dense, out, 32, r, r, N, N, N) == COALAC_EINVAL && says("NULL"));
+    CHECK(coalac_decode_packed(&p.sparse, out, 32, r, r, N, x, N) == COALAC_EINVAL && says("dense plan"));
+    CHECK(coalac_decode_packed(&p.raw, out, 32, r, r, N, x, N) == COALAC_EINVAL && says("bits == 32"));
+    CHECK(coalac_decode_packed(&p.dense, out, 28, r, r, N, x, N) == COALAC_EINVAL && says("packed_bytes"));
+    CHECK(coalac_decode_packed(&p.dense, bytes + 2, 32, r, r, N, x, N) == COALAC_EINVAL && says("4-byte"));
+    CHECK(coalac_decode_packed(&p.dense, out, 32, r, r, N, x + 1, N) == COALAC_EINVAL && says("16-byte"));
+    CHECK(coalac_decode_packed(&p.dense, out, 32, r, r, x + 2, x, N) == COALAC_EINVAL && says("16-byte"));
+  }
+  // the plan without units, otherwise: OK with nothing launched (a launch on this host-memory plan would fail)
+  CHECK(coalac_pack_dense(&p.dense, x, out, 32, N) == COALAC_OK);
+  CHECK(coalac_unpack_dense(&p.dense, out, 32, x, N) == COALAC_OK);
+  CHECK(coalac_decode_packed(&p.dense, out, 32, r, r, N, x, N) == COALAC_OK);
+  CHECK(coalac_decode_packed(&p.dense, out, 32, r, r, x, x, N) == COALAC_OK);
+  for (int i = 0; i < 64; ++i) CHECK(x[i] == 0.0f && out[i] == 0u);  // nothing was written
 }
 
 static size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
@@ -169,8 +210,8 @@ static void table_walk() {
 int main() {
   plan_validation();
   null_arguments();
+  dense_stream();
   workspace_walk();
   table_walk();
-  printf(g_failures ? "host checks: %d FAILED\n" : "host checks: ok\n", g_failures);
-  return g_failures ? 1 : 0;
+  return report("host checks");
 }

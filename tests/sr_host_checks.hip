@@ -11,16 +11,7 @@
 
 #include <cinttypes>
 
-static int g_failures = 0;
-#define CHECK(cond)                                                     \
-  do {                                                                  \
-    if (!(cond)) {                                                      \
-      printf("FAILED %s:%d: %s [%s]\n", __FILE__, __LINE__, #cond, coalac_last_error()); \
-      ++g_failures;                                                     \
-    }                                                                   \
-  } while (0)
-
-static bool says(const char* part) { return strstr(coalac_last_error(), part) != nullptr; }
+#include "host_check_common.h"
 
 static void model_table(const char* path) {
   FILE* f = fopen(path, "r");
@@ -69,13 +60,8 @@ static void known_answers() {
 }
 
 static void argument_checks() {
-  coalac_plan dense, sparse, raw;  // (in host memory: every check below returns before the first device call)
-  for (coalac_plan* p : {&dense, &sparse, &raw}) {
-    p->dense = true, p->bits = 4, p->proto.nseg = 1, p->proto.n_units = 1, p->total_k = 64, p->span = 64;
-    p->ws_bytes = 256, p->dense_words = 8;
-  }
-  sparse.dense = false;
-  raw.bits = 32;
+  HostPlans p;
+  coalac_plan &dense = p.dense, &sparse = p.sparse, &raw = p.raw;
   alignas(16) static float x[64];
   alignas(16) static uint32_t out[64];
   const float* seg = x;
@@ -108,8 +94,9 @@ static void argument_checks() {
   CHECK(coalac_encode_block_sr(&dense, x + 1, N, N, r, r, out, 32, 1, N) == COALAC_EINVAL && says("16-byte"));
   CHECK(coalac_encode_block_sr(&dense, x, N, N, r, r, reinterpret_cast<uint8_t*>(out) + 2, 32, 1, N) == COALAC_EINVAL &&
         says("4-byte"));
-  // a plan without segments / units: OK, nothing launched
-  dense.proto.nseg = 0, dense.proto.n_units = 0;
+  // a plan without segments / units: the block-wise checks are the same, else OK, nothing launched
+  p.empty_dense();
+  CHECK(coalac_encode_block_sr(&dense, x + 1, N, N, r, r, out, 32, 1, N) == COALAC_EINVAL && says("16-byte"));
   CHECK(coalac_encode_sr(&dense, x, N, N, out, r, r, ws, 256, 1, 0, N) == COALAC_OK);
   CHECK(coalac_encode_block_sr(&dense, x, N, N, r, r, out, 32, 1, N) == COALAC_OK);
 }
@@ -122,6 +109,5 @@ int main(int argc, char** argv) {
   model_table(argv[1]);
   known_answers();
   argument_checks();
-  printf(g_failures ? "sr host checks: %d FAILED\n" : "sr host checks: ok\n", g_failures);
-  return g_failures ? 1 : 0;
+  return report("sr host checks");
 }

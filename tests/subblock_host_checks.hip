@@ -1,36 +1,20 @@
 // Host-side checks of the block-size entry points that need no device (tests/test_subblock_host.py
 // builds and runs it, with the host sanitizers): every COALAC_EINVAL case of coalac_encode_block_g,
-// coalac_decode_block_g, coalac_aggregate_dense_g and coalac_plan_block_count, each of which returns before the first
-// device call, on plans built in host memory; the plan without units; and the block counts against hand-computed ones.
+// coalac_decode_block_g, coalac_aggregate_dense_g and coalac_plan_block_count — and, through block = 4096, of
+// coalac_encode_block, coalac_decode_block and coalac_aggregate_dense — each of which returns before the first device
+// call, on plans built in host memory; the plan without units; and the block counts against hand-computed ones.
 // The codec source is included, not linked: struct coalac_plan lives in it.
 #include "../coala_amd/csrc/coalac.hip"
 
-static int g_failures = 0;
-#define CHECK(cond)                                                     \
-  do {                                                                  \
-    if (!(cond)) {                                                      \
-      printf("FAILED %s:%d: %s [%s]\n", __FILE__, __LINE__, #cond, coalac_last_error()); \
-      ++g_failures;                                                     \
-    }                                                                   \
-  } while (0)
-
-static bool says(const char* part) { return strstr(coalac_last_error(), part) != nullptr; }
+#include "host_check_common.h"
 
 alignas(16) static float x[64];
 alignas(16) static uint32_t out[64];
 alignas(16) static const void* ptrs[4];
 
-static void make(coalac_plan& p) {
-  p.dense = true, p.bits = 4, p.proto.nseg = 1, p.proto.n_units = 1, p.total_k = 64, p.span = 64;
-  p.ws_bytes = 256, p.dense_words = 8;
-  p.n_blocks[0] = 1, p.n_blocks[1] = 1;
-}
-
 static void block_counts() {
-  coalac_plan p, sparse, raw;
-  for (coalac_plan* q : {&p, &sparse, &raw}) make(*q);
-  sparse.dense = false;
-  raw.bits = 32;
+  HostPlans hp;
+  coalac_plan &p = hp.dense, &sparse = hp.sparse, &raw = hp.raw;
   // the counts a plan over segments of 0, 1, 255, 256, 257 and 4097 elements holds: 22 blocks of 256 (0 + 1 + 1 + 1 + 2
   // + 17), 9 of 1024 (0 + 1 + 1 + 1 + 1 + 5), 6 units (0 + 1 + 1 + 1 + 1 + 2)
   const uint32_t sizes[6] = {0, 1, 255, 256, 257, 4097};
@@ -56,10 +40,8 @@ static void block_counts() {
 }
 
 static void encode_and_decode(uint32_t G) {
-  coalac_plan dense, sparse, raw;
-  for (coalac_plan* p : {&dense, &sparse, &raw}) make(*p);
-  sparse.dense = false;
-  raw.bits = 32;
+  HostPlans hp;
+  coalac_plan &dense = hp.dense, &sparse = hp.sparse, &raw = hp.raw;
   const float* seg = x;
   const auto N = nullptr;
   float* r = reinterpret_cast<float*>(out);
@@ -96,9 +78,13 @@ static void encode_and_decode(uint32_t G) {
   CHECK(coalac_decode_block_g(&dense, G, out, 32, r, r, N, x + 1, N) == COALAC_EINVAL && says("16-byte"));
   CHECK(coalac_decode_block_g(&dense, G, out, 32, r, r, x + 2, x, N) == COALAC_EINVAL && says("16-byte"));
   // a plan without units: the same checks, else OK with nothing launched (a launch on this host-memory plan would fail)
-  dense.proto.nseg = 0, dense.proto.n_units = 0;
+  hp.empty_dense();
   CHECK(coalac_encode_block_g(&dense, G, x, N, N, N, r, out, 32, N) == COALAC_EINVAL && says("NULL"));
   CHECK(coalac_decode_block_g(&dense, G, out, 32, r, r, N, N, N) == COALAC_EINVAL && says("NULL"));
+  CHECK(coalac_encode_block_g(&dense, G, x + 1, N, N, r, r, out, 32, N) == COALAC_EINVAL && says("16-byte"));
+  CHECK(coalac_encode_block_g(&dense, G, x, N, N, r, r, bytes + 2, 32, N) == COALAC_EINVAL && says("4-byte"));
+  CHECK(coalac_decode_block_g(&dense, G, bytes + 2, 32, r, r, N, x, N) == COALAC_EINVAL && says("4-byte"));
+  CHECK(coalac_decode_block_g(&dense, G, out, 32, r, r, N, x + 1, N) == COALAC_EINVAL && says("16-byte"));
   CHECK(coalac_encode_block_g(&dense, G, x, N, N, r, r, out, 32, N) == COALAC_OK);
   CHECK(coalac_encode_block_g(&dense, G, N, &seg, x, r, r, out, 32, N) == COALAC_OK);
   CHECK(coalac_decode_block_g(&dense, G, out, 32, r, r, N, x, N) == COALAC_OK);
@@ -106,10 +92,8 @@ static void encode_and_decode(uint32_t G) {
 }
 
 static void aggregate(uint32_t G) {
-  coalac_plan dense, sparse, raw;
-  for (coalac_plan* p : {&dense, &sparse, &raw}) make(*p);
-  sparse.dense = false;
-  raw.bits = 32;
+  HostPlans hp;
+  coalac_plan &dense = hp.dense, &sparse = hp.sparse, &raw = hp.raw;
   const auto N = nullptr;
   const void* const* cp = ptrs;
   const float* const* fp = reinterpret_cast<const float* const*>(ptrs);
@@ -136,7 +120,7 @@ static void aggregate(uint32_t G) {
                                  x, N) == COALAC_EINVAL && says("8-byte"));
   CHECK(coalac_aggregate_dense_g(&dense, 1, G, cp, 32, fp, fp, reinterpret_cast<const float*>(bytes + 2), 1.0f, DIV, N, N, x,
                                  N) == COALAC_EINVAL && says("4-byte"));
-  dense.proto.nseg = 0, dense.proto.n_units = 0;
+  hp.empty_dense();
   CHECK(coalac_aggregate_dense_g(&dense, 1, G, cp, 32, fp, fp, w, 1.0f, DIV, N, N, N, N) == COALAC_EINVAL && says("NULL"));
   CHECK(coalac_aggregate_dense_g(&dense, 1, G, cp, 32, fp, fp, w, 1.0f, DIV, N, N, x, N) == COALAC_OK);
   CHECK(coalac_aggregate_dense_g(&dense, 2, G, cp, 32, fp, fp, w, 1.0f, COALAC_AGG_SUM, N, x, x, N) == COALAC_OK);
@@ -144,9 +128,9 @@ static void aggregate(uint32_t G) {
 }
 
 static void bad_block_sizes() {
-  coalac_plan dense;
-  make(dense);
-  dense.proto.nseg = 0, dense.proto.n_units = 0;  // (every other argument is acceptable: only the size is wrong)
+  HostPlans hp;
+  coalac_plan& dense = hp.dense;
+  hp.empty_dense();  // (every other argument is acceptable: only the size is wrong)
   const auto N = nullptr;
   float* r = reinterpret_cast<float*>(out);
   const void* const* cp = ptrs;
@@ -162,11 +146,9 @@ static void bad_block_sizes() {
 
 int main() {
   block_counts();
-  for (uint32_t G : {256u, 1024u}) encode_and_decode(G);
-  // (4096 forwards to the twins; coalac_aggregate_dense, like the entry points above, checks everything before its
-  // first device call, so its cases run here too)
-  for (uint32_t G : {256u, 1024u, 4096u}) aggregate(G);
+  // (4096 forwards to the twins — coalac_encode_block, coalac_decode_block, coalac_aggregate_dense — which, like the
+  // entry points above, check everything before their first device call, so their cases run here too)
+  for (uint32_t G : {256u, 1024u, 4096u}) encode_and_decode(G), aggregate(G);
   bad_block_sizes();
-  printf(g_failures ? "subblock host checks: %d FAILED\n" : "subblock host checks: ok\n", g_failures);
-  return g_failures ? 1 : 0;
+  return report("subblock host checks");
 }

@@ -1,27 +1,14 @@
 """The codec's host code under AddressSanitizer + UndefinedBehaviorSanitizer, without Python in the process and
 without a GPU: tests/host_checks.hip (a stand-alone program that includes coalac.hip) is built with the host
-sanitizers and run as a child process. It covers what returns before any device call — plan validation, the
-NULL-argument cases of every entry point — and the workspace / plan-table walks on host buffers of exactly the
-measured size. The device code in the binary is never run (built at -O0 to keep the compile short)."""
-import os
-import subprocess
-
-from coala_amd import _build
-
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_checks.hip")
-SANITIZE = "-fsanitize=address,undefined"
+sanitizers and run as a child process (tests/host_program.py). It covers what returns before any device call — plan
+validation, the NULL-argument cases of every entry point, every COALAC_EINVAL case of coalac_pack_dense,
+coalac_unpack_dense and coalac_decode_packed — and the workspace / plan-table walks on host buffers of exactly the
+measured size."""
+from tests.host_program import build_and_run
 
 
 def test_host_code_is_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "host_checks")
-    cmd = [_build.hipcc(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", f"--offload-arch={_build.ARCH}",
-           "-Xarch_device", "-O0", "-Xarch_device", "-g0", "-Xarch_host", SANITIZE,
-           "-Xarch_host", "-fno-sanitize-recover=undefined", SANITIZE,  # (the last one: the link's runtime)
-           "-Wno-option-ignored", "-Wno-pass-failed", "-o", exe, SRC]
-    built = subprocess.run(cmd, capture_output=True, text=True)
+    built, run = build_and_run("host_checks", tmp_path)
     assert built.returncode == 0, built.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
     assert run.returncode == 0 and "host checks: ok" in run.stdout, (run.stdout[-4000:], run.stderr[-4000:])
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error:" not in run.stderr, run.stderr[-4000:]

@@ -4,16 +4,10 @@ tests/sr_host_checks.hip (a stand-alone program that includes coalac.hip) is bui
 -ffp-contract=off, and run as a child process over a table of draws and codes this test writes from the model —
 seeds, positions on both sides of 2^32, quotients at and next to integers, NaN, infinities and the ends of the range.
 The device code in the binary is never run (built at -O0 to keep the compile short)."""
-import os
-import subprocess
-
 import numpy as np
 
-from coala_amd import _build
 from tests import sr_model as M
-
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "sr_host_checks.hip")
-SANITIZE = "-fsanitize=address,undefined"
+from tests.host_program import build_and_run
 
 
 def _table(path):
@@ -42,16 +36,9 @@ def _table(path):
 
 
 def test_kernel_source_matches_the_model_and_checks_its_arguments(tmp_path):
-    exe, table = str(tmp_path / "sr_host_checks"), str(tmp_path / "table.txt")
+    table = str(tmp_path / "table.txt")
     _table(table)
-    cmd = [_build.hipcc(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", f"--offload-arch={_build.ARCH}",
-           "-Xarch_device", "-O0", "-Xarch_device", "-g0", "-Xarch_host", SANITIZE,
-           "-Xarch_host", "-fno-sanitize-recover=undefined", SANITIZE,  # (the last one: the link's runtime)
-           "-Wno-option-ignored", "-Wno-pass-failed", "-o", exe, SRC]
-    built = subprocess.run(cmd, capture_output=True, text=True)
+    built, run = build_and_run("sr_host_checks", tmp_path, table)
     assert built.returncode == 0, built.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    run = subprocess.run([exe, table], capture_output=True, text=True, env=env, timeout=120)
     assert run.returncode == 0 and "sr host checks: ok" in run.stdout, (run.stdout[-4000:], run.stderr[-4000:])
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error:" not in run.stderr, run.stderr[-4000:]
