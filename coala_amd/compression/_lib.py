@@ -79,6 +79,11 @@ SIGNATURES = [
     ("coalac_encode_block_g", _I, [_P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _U64, _P]),
     ("coalac_decode_block_g", _I, [_P, ctypes.c_uint32, _P, _U64, _P, _P, _P, _P, _P]),
     ("coalac_aggregate_dense_g", _I, [_P, _I, ctypes.c_uint32, _P, _U64, _P, _P, _P, ctypes.c_float, _I, _P, _P, _P, _P]),
+    # rotated block-wise: coalac_encode_block's arguments with rot_seed (and the SR seed) ahead of the
+    # stream / coalac_decode_block's with rot_seed behind bscale
+    ("coalac_encode_block_rot", _I, [_P, _P, _P, _P, _P, _P, _P, _U64, _U64, _P]),
+    ("coalac_encode_block_rot_sr", _I, [_P, _P, _P, _P, _P, _P, _P, _U64, _U64, _U64, _P]),
+    ("coalac_decode_block_rot", _I, [_P, _P, _U64, _P, _P, _U64, _P, _P, _P]),
     ("coalac_encode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, ctypes.c_uint, _P, _P]),
     ("coalac_decode_ev", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # aggregate: plan, clients, idx, vals, mn, scale, ustart, weights, total, mode, mask, base, out, stream (+ events)
@@ -100,7 +105,9 @@ ABI_VERSION = 11
 # variant of an earlier commit) loads without them, and only a call that needs one fails
 ADDED_FOR_BLOCK_SIZES = ("coalac_plan_block_count", "coalac_encode_block_g", "coalac_decode_block_g",
                          "coalac_aggregate_dense_g")
-ADDED_IN_ABI_11 = ("coalac_encode_sr", "coalac_encode_block_sr", "coalac_encode_block_ef") + ADDED_FOR_BLOCK_SIZES
+ADDED_FOR_ROTATION = ("coalac_encode_block_rot", "coalac_encode_block_rot_sr", "coalac_decode_block_rot")
+ADDED_IN_ABI_11 = (("coalac_encode_sr", "coalac_encode_block_sr", "coalac_encode_block_ef") + ADDED_FOR_BLOCK_SIZES
+                   + ADDED_FOR_ROTATION)
 
 
 class CodecError(RuntimeError):

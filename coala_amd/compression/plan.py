@@ -559,9 +559,10 @@ class CodecPlan:
             raise _lib.CodecError(f"the loaded codec library has no {name} (built before {since})")
         return fn
 
-    def _encode_block(self, who, seed, flat, tensors, base, out, stream, checked, ptrs, resid=None, block=UNIT):
+    def _encode_block(self, who, seed, flat, tensors, base, out, stream, checked, ptrs, resid=None, block=UNIT,
+                      rot_seed=None):
         # encode_block / encode_block_sr (seed None: the deterministic entry point) / encode_block_ef (resid given) /
-        # encode_block_g (block below 4096)
+        # encode_block_g (block below 4096) / encode_block_rot (rot_seed given; seed None: round to nearest)
         self._need_dense(who)
         if (flat is None) == (tensors is None):
             raise ValueError(f"{who}: give exactly one of flat and tensors")
@@ -585,7 +586,13 @@ class CodecPlan:
         self._check_dense_packed(packed, "packed output")
         args = (self._h, x, seg, _ptr(base), _ptr(bmn), _ptr(bscale), _ptr(packed), ctypes.c_uint64(4 * packed.numel()))
         st = ctypes.c_void_p(launch.cuda_stream)
-        if block != UNIT:
+        if rot_seed is not None:
+            who = "encode_block_rot" if seed is None else "encode_block_rot_sr"
+            fn = self._sr_entry("coalac_" + who, since="the rotated block-wise quantisation")
+            seeds = [ctypes.c_uint64(int(s) & 0xFFFFFFFFFFFFFFFF) for s in ((rot_seed,) if seed is None else (rot_seed, seed))]
+            with _device_ctx(self.device):
+                rc = fn(*args, *seeds, st)
+        elif block != UNIT:
             with _device_ctx(self.device):
                 rc = self._lib.coalac_encode_block_g(self._h, ctypes.c_uint32(block), *args[1:], st)
         elif ef:
@@ -601,6 +608,34 @@ class CodecPlan:
                 rc = fn(*args, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), st)
         _lib.check(rc, "coalac_" + who)
         return bmn, bscale, packed
+
+    # -- rotated block-wise quantisation -------------------------------------------
+    @property
+    def has_block_rot(self):
+        """Whether the loaded library exports the rotated entry points (an ABI-11 build from before them does not)."""
+        return all(hasattr(self._lib, n) for n in _lib.ADDED_FOR_ROTATION)
+
+    def encode_block_rot(self, flat=None, tensors=None, base=None, rot_seed=0, seed=None, out=None, stream=None,
+                         checked=False, ptrs=None):
+        """encode_block with every full 4096-element unit rotated first (coalac_encode_block_rot): a sign
+        diagonal drawn from `rot_seed` (64 bits) and the orthonormal Walsh-Hadamard transform, the coefficients quantised
+        as encode_block quantises the values; a unit shorter than 4096 is encode_block's. seed: None rounds to nearest,
+        a 64-bit seed rounds stochastically as encode_block_sr does (coalac_encode_block_rot_sr). The triple has
+        encode_block's shapes; only decode_block_rot with the same rot_seed reads it. Asynchronous on `stream`."""
+        return self._encode_block("encode_block_rot", seed, flat, tensors, base, out, stream, checked, ptrs,
+                                  rot_seed=rot_seed)
+
+    def decode_block_rot(self, packed, bmn, bscale, rot_seed, base=None, out=None, stream=None):
+        """Decode of a rotated block-wise stream (coalac_decode_block_rot): decode_block, then the inverse rotation of
+        every full unit under `rot_seed` -> dense flat fp32[span] (+ base, fused). Asynchronous on `stream`."""
+        raw = self._sr_entry("coalac_decode_block_rot", since="the rotated block-wise quantisation")
+        rs = ctypes.c_uint64(int(rot_seed) & 0xFFFFFFFFFFFFFFFF)
+
+        def fn(h, packed_p, nbytes, r0, r1, *rest):
+            return raw(h, packed_p, nbytes, r0, r1, rs, *rest)
+        fn.__name__ = "coalac_decode_block_rot"
+        return self._decode_stream(fn, "decode_block_rot", self.n_units, "bmn / bscale", packed, bmn, bscale, base, out,
+                                   stream)
 
     # -- block-wise with 256- and 1024-element blocks (DESIGN.md §20) ------------------------------
     BLOCK_SIZES = (256, 1024, UNIT)

@@ -71,6 +71,18 @@ Version 5, BLOCK-WISE DENSE QUANTISATION (opt-in, "dense" updates with bits 1..8
     [G g_s, min(n_s, G (g_s + 1))), mn / scale of length NB; the code stream does not change. A blob with
     "blockwise": 4096 is byte for byte what it was before the other two sizes existed. No other size is defined.
 
+Version 6, ROTATED BLOCK-WISE QUANTISATION (opt-in; header keys "dense": true, "blockwise": 4096, "n_blocks": U and
+"rotate": the call's rotation seed, an integer in [0, 2^64)):
+         mn f32[U] | scale f32[U] | packed u32[P] | raw bytes
+    Version 5's sections at block size 4096, byte for byte in layout and length; what differs is what the codes mean.
+    Every block of exactly 4096 elements holds the codes of its Walsh-Hadamard coefficients under the sign diagonal of
+    the "rotate" seed, and a decoder applies the inverse after dequantising; a shorter block (a
+    segment's ragged end, a small tensor) is version 5's. It is a version of its own, not a version-5 blob with one
+    more key, because a reader from before it would decode the coefficients as values and return garbage without a
+    word: the version word makes it refuse. "rotate" is rejected without "blockwise", with a block size other than 4096,
+    with a seed that is not an integer (a bool is not) in range, and with "dense_packed", "compact" or "n_units".
+    unpack() returns mn / scale of length U and the rebuilt uint8 codes of the coefficients.
+
 The executable form of the above is the table FORMATS below: one record per version with the version's ordered
 sections (name, dtype, element count) and its header rules. format_of(header) picks the record — nothing else in the
 package reads the format keys — and is_dense(header) says whether the indices are implied. pack, sections and unpack are
@@ -93,6 +105,7 @@ VERSION_2 = 2   # ... | vals | ustart | raw
 VERSION_3 = 3   # mn | scale | packed | [vals f32] | ustart | raw  (header "compact": true)
 VERSION_4 = 4   # mn | scale | packed | raw  (header "dense": true, "dense_packed": true)
 VERSION_5 = 5   # mn[U] | scale[U] | packed | raw  (header "dense": true, "blockwise": 256 | 1024 | 4096, "n_blocks": U)
+VERSION_6 = 6   # version 5's sections at "blockwise": 4096, the full blocks rotated (header "rotate": the seed)
 BLOCK_SIZES = (256, 1024, UNIT)  # the block sizes "blockwise" may name
 INDEX_BITS = 12  # low index bits in a packed field: log2(UNIT), the position inside the entry's 4096-element unit
 
@@ -355,15 +368,34 @@ def _v5_rules(h, dense, layout):
         raise ValueError("COALAQ1: header n_blocks is not the layout's block count")
 
 
+def check_rotate_seed(seed):
+    """`seed` as an int if it is an integer in [0, 2^64) (a bool is not a seed), else ValueError."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"COALAQ1: \"rotate\" is the rotation seed, an integer in [0, 2^64), not {seed!r}")
+    return int(seed)
+
+
+def _v6_rules(h, dense, layout):
+    if "blockwise" not in h:
+        raise ValueError("COALAQ1: \"rotate\" needs a \"blockwise\" payload")
+    _v5_rules(h, dense, layout)
+    if h["blockwise"] != UNIT:
+        raise ValueError(f"COALAQ1: \"rotate\" is defined for {UNIT}-element blocks only, not {h['blockwise']}")
+    check_rotate_seed(h["rotate"])
+
+
 FORMATS = (Format(VERSION, None, False, _v1_sections, None),
            Format(VERSION_2, None, False, _v2_sections, None),
            Format(VERSION_3, "entries", False, _v3_sections, _v3_rules),
            Format(VERSION_4, "dense", False, _v4_sections, _v4_rules),
-           Format(VERSION_5, "dense", True, _v5_sections, _v5_rules))
+           Format(VERSION_5, "dense", True, _v5_sections, _v5_rules),
+           Format(VERSION_6, "dense", True, _v5_sections, _v6_rules))
 
 
 def format_of(header):
     """The Format a header describes: the one place that reads the format keys, in their order of precedence."""
+    if "rotate" in header:
+        return FORMATS[5]
     if "blockwise" in header:
         return FORMATS[4]
     if header.get("dense_packed"):
@@ -485,7 +517,7 @@ def unpack(blob):
     mv, ver, header, pos = _open(blob)
     fmt = format_of(header)
     if fmt.version != ver:
-        raise ValueError(f"COALAQ1: version word {ver}, but the header's keys (\"blockwise\", \"dense_packed\", "
+        raise ValueError(f"COALAQ1: version word {ver}, but the header's keys (\"rotate\", \"blockwise\", \"dense_packed\", "
                          f"\"compact\", \"n_units\") describe version {fmt.version}")
     check_header(header, on_wire=True)
     secs, raw_at = _section_offsets(section_list(header, on_wire=True), pos)

@@ -3810,15 +3810,121 @@ DEV void ef_unit_load(const Params& P, const UnitDev& U, float4 (&v)[UNIT_IT]) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Rotated block-wise quantisation: a full unit (len == UNIT) is multiplied by a pseudo-random sign
+// diagonal and by the orthonormal Walsh-Hadamard matrix of order 4096 before it is quantised, and by both again, in the
+// other order, after it is dequantised (the matrix is its own inverse). A unit shorter than UNIT is not rotated.
+//   signs      element e of the unit at flat position c0 has its sign bit inverted where bit 23 of sr_u24(rot_seed,
+//              c0 + e) is set: §18's hash under a seed of its own, an XOR on the bit pattern whatever the value is
+//   transform  for h = 1, 2, 4, ..., 2048 in this order, every pair (i, i + h) with i & h == 0 becomes (t[i] + t[i+h],
+//              t[i] - t[i+h]), fp32 adds and subtracts only; then every value * 2^-6
+// Element e = (it * 64 + lane) * 4 + j lies in register r = 4 it + j of its lane: h = 1, 2 pair registers (j), h = 4 ..
+// 128 pair lanes l and l ^ (h / 4), h = 256 .. 2048 pair registers again (it). A lane pair inside a row of 16 moves by
+// DPP: the upper lane's value is p - t, computed as p + (-t), the same IEEE operation. Lanes 16 and 32 apart move by
+// gfx950's half-exchange swaps, two registers a, b at a time: after swap(a, b) the lower lanes of a pair hold both
+// halves of a's pair and the upper lanes both of b's, so one add and one subtract are the butterflies of both
+// registers, and a second swap of (sum, difference) puts every result back in its lane. No select, no LDS.
+// ------------------------------------------------------------------------------------------------
+constexpr float ROT_NORM = 0.015625f;  // 1 / sqrt(4096)
+
+template <uint32_t K>
+DEV float rot_lane_xor(float x) {  // lane l reads lane l ^ K, K < 16: inside a DPP row
+  static_assert(K == 1 || K == 2 || K == 4 || K == 8, "a lane pair inside a row of 16");
+  const uint32_t v = __float_as_uint(x);
+  if constexpr (K == 1) return __uint_as_float(dpp<0xB1>(v));  // quad_perm [1, 0, 3, 2]
+  if constexpr (K == 2) return __uint_as_float(dpp<0x4E>(v));  // quad_perm [2, 3, 0, 1]
+  if constexpr (K == 4) return __uint_as_float(dpp<0x1B>(dpp<0x141>(v)));  // l ^ 7 (row_half_mirror), then l ^ 3
+  return __uint_as_float(dpp<0x128>(v));                       // row_ror:8
+}
+
+template <uint32_t K>
+DEV void rot_stage_dpp(float (&t)[UNIT_IT * 4], uint32_t lane) {
+  const uint32_t neg = (lane & K) ? 0x80000000u : 0u;
+#pragma unroll
+  for (uint32_t r = 0; r < UNIT_IT * 4; ++r)
+    t[r] = rot_lane_xor<K>(t[r]) + __uint_as_float(__float_as_uint(t[r]) ^ neg);
+}
+
+template <bool HALF>  // lanes 32 apart (HALF), else 16 apart
+DEV void rot_swap(float& a, float& b) {
+  const uint32_t x = __float_as_uint(a), y = __float_as_uint(b);
+  if constexpr (HALF) {
+    const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+    a = __uint_as_float(r[0]), b = __uint_as_float(r[1]);
+  } else {
+    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+    a = __uint_as_float(r[0]), b = __uint_as_float(r[1]);
+  }
+}
+
+template <bool HALF>
+DEV void rot_stage_swap(float (&t)[UNIT_IT * 4]) {
+#pragma unroll
+  for (uint32_t r = 0; r < UNIT_IT * 4; r += 2) {
+    float a = t[r], b = t[r + 1];
+    rot_swap<HALF>(a, b);
+    float s = a + b, d = a - b;
+    rot_swap<HALF>(s, d);
+    t[r] = s, t[r + 1] = d;
+  }
+}
+
+template <uint32_t S>  // registers S apart
+DEV void rot_stage_reg(float (&t)[UNIT_IT * 4]) {
+#pragma unroll
+  for (uint32_t r = 0; r < UNIT_IT * 4; ++r)
+    if ((r & S) == 0) {
+      const float s = t[r] + t[r + S], d = t[r] - t[r + S];
+      t[r] = s, t[r + S] = d;
+    }
+}
+
+// the transform of a full unit in its lanes' registers (encode and decode: the one copy)
+DEV void rot_hadamard(float4 (&v)[UNIT_IT], uint32_t lane) {
+  float t[UNIT_IT * 4];
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it)
+    t[4 * it] = v[it].x, t[4 * it + 1] = v[it].y, t[4 * it + 2] = v[it].z, t[4 * it + 3] = v[it].w;
+  rot_stage_reg<1>(t);
+  rot_stage_reg<2>(t);
+  rot_stage_dpp<1>(t, lane);
+  rot_stage_dpp<2>(t, lane);
+  rot_stage_dpp<4>(t, lane);
+  rot_stage_dpp<8>(t, lane);
+  rot_stage_swap<false>(t);
+  rot_stage_swap<true>(t);
+  rot_stage_reg<4>(t);
+  rot_stage_reg<8>(t);
+  rot_stage_reg<16>(t);
+  rot_stage_reg<32>(t);
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it)
+    v[it] = make_float4(t[4 * it] * ROT_NORM, t[4 * it + 1] * ROT_NORM, t[4 * it + 2] * ROT_NORM, t[4 * it + 3] * ROT_NORM);
+}
+
+// the sign diagonal of a full unit whose first element is at flat position c0
+DEV void rot_signs(float4 (&v)[UNIT_IT], uint64_t rot_seed, uint64_t c0, uint32_t lane) {
+  const SrUnit sr = sr_unit(rot_seed, c0, UNIT);
+  auto flip = [&](float x, uint32_t e) { return __uint_as_float(__float_as_uint(x) ^ ((sr_draw(sr, e) & 0x800000u) << 8)); };
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    const uint32_t e0 = (it * 64 + lane) * 4;
+    v[it] = make_float4(flip(v[it].x, e0), flip(v[it].y, e0 + 1), flip(v[it].z, e0 + 2), flip(v[it].w, e0 + 3));
+  }
+}
+
 // SR: stochastic rounding, as dense_quant_unit's. EF: error feedback in the same pass:
 // the unit quantised is a = (x - base) + r, and r (P.out, laid out like the input) leaves as ef_residual(a, xhat).
 // G: the block size: 4096, the unit itself, or 256 / 1024 — a block is then G / 256 of the unit's rows,
 // its range one wave reduction pair, written at dense_block_index (gb: the plan's block table for G).
-template <bool DELTA, uint32_t B, bool XCD, bool SR, bool EF = false, uint32_t G = UNIT>
+// ROT: a full unit is rotated between the load and the min / max (rot_signs under rot_seed, then
+// rot_hadamard), behind a wave-uniform len == UNIT; everything from the min / max on sees the coefficients.
+template <bool DELTA, uint32_t B, bool XCD, bool SR, bool EF = false, uint32_t G = UNIT, bool ROT = false>
 DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw, float* __restrict__ bmn,
                                 float* __restrict__ bscale, uint32_t* __restrict__ packed, uint64_t seed,
-                                const uint64_t* __restrict__ gb = nullptr) {
+                                const uint64_t* __restrict__ gb = nullptr, uint64_t rot_seed = 0) {
   static_assert(!(SR && EF), "stochastic rounding and error feedback are not combined (DESIGN.md §18)");
+  static_assert(!ROT || (!EF && G == UNIT), "the rotation: 4096-element blocks, no error feedback (DESIGN.md §22)");
   static_assert(G == UNIT || (!SR && !EF && (G == 256u || G == 1024u)),
                 "blocks below the unit: 256 or 1024 elements, deterministic only (DESIGN.md §20)");
   constexpr uint32_t FB = 4u * B;                    // bits per field
@@ -3836,6 +3942,12 @@ DEV void dense_block_quant_unit(const Params& P, const uint64_t* __restrict__ pw
     ef_unit_load<DELTA>(P, U, v);
   else
     dense_unit_load<DELTA, DENSE_Q_AUX>(P, U, v);
+  if constexpr (ROT) {
+    if (__builtin_amdgcn_readfirstlane(len) == UNIT) {
+      rot_signs(v, rot_seed, U.off, lane);
+      rot_hadamard(v, lane);
+    }
+  }
   float a, b, mn, scale;
   if constexpr (G == UNIT) {
     dense_unit_minmax(v, len, lane, a, b);
@@ -3958,6 +4070,51 @@ __global__ __launch_bounds__(BLOCK) void k_dense_block_quant_sr(Params P, const 
                                                                 float* __restrict__ bmn, float* __restrict__ bscale,
                                                                 uint32_t* __restrict__ packed, uint64_t seed) {
   dense_block_quant_unit<DELTA, B, XCD, true>(P, pw, bmn, bscale, packed, seed);
+}
+
+// ... with the rotation of full units, rounding to nearest or (SR) stochastically under `seed`
+template <bool DELTA, uint32_t B, bool XCD, bool SR>
+__global__ __launch_bounds__(BLOCK) void k_dense_block_quant_rot(Params P, const uint64_t* __restrict__ pw,
+                                                                 float* __restrict__ bmn, float* __restrict__ bscale,
+                                                                 uint32_t* __restrict__ packed, uint64_t rot_seed,
+                                                                 uint64_t seed) {
+  dense_block_quant_unit<DELTA, B, XCD, SR, false, UNIT, true>(P, pw, bmn, bscale, packed, seed, nullptr, rot_seed);
+}
+
+// The decode of a rotated stream: one wave per unit with the unit's 64 values per lane resident —
+// dequantise, the inverse rotation of a full unit (rot_hadamard, then rot_signs: each its own inverse), base + x, the
+// stores range-checked to the unit. A unit shorter than UNIT is k_dense_deq_stream<PERUNIT>'s, value for value. The unit
+// as a scalar, as k_dense_deq_stream_g: its record and its range are scalar loads.
+template <uint32_t B, bool HASBASE, bool XCD>
+__global__ __launch_bounds__(BLOCK) void k_dense_deq_stream_rot(Params P, const uint64_t* __restrict__ pw,
+                                                                const uint32_t* __restrict__ packed,
+                                                                const float* __restrict__ rmn,
+                                                                const float* __restrict__ rscale, uint64_t rot_seed) {
+  const uint32_t u =
+      __builtin_amdgcn_readfirstlane((XCD ? xcd_block(blockIdx.x) : blockIdx.x) * WAVES + (threadIdx.x >> 6));
+  if (u >= P.n_units) return;
+  const UnitDev U = P.units[u];
+  const uint32_t lane = lane_id();
+  const float mn = rmn[u], scale = rscale[u];
+  const __amdgpu_buffer_rsrc_t rin = dense_unit_words_rsrc<B>(packed, pw, U);
+  uint32_t lo[UNIT_IT], hi[UNIT_IT];
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) dense_row_words<B>(rin, it, lane, lo[it], hi[it]);
+  const __amdgpu_buffer_rsrc_t rout = unit_rsrc(P.out + U.off, U.len);
+  const __amdgpu_buffer_rsrc_t rb = unit_rsrc(HASBASE ? P.base + U.off : P.out + U.off, U.len);
+  float4 v[UNIT_IT];
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) v[it] = dense_row_values<B>(lo[it], hi[it], it, lane, mn, scale);
+  if (U.len == UNIT) {  // (wave-uniform: U is scalar)
+    rot_hadamard(v, lane);
+    rot_signs(v, rot_seed, U.off, lane);
+  }
+#pragma unroll
+  for (uint32_t it = 0; it < UNIT_IT; ++it) {
+    float4 x = v[it];
+    if (HASBASE) x = dense_add_base(unit_load_x4<false>(rb, rb, (it * 64 + lane) * 16), x);
+    dense_store_row(rout, U.len, it, lane, x);
+  }
 }
 
 // ... with G-element blocks below the unit: gb is the plan's block table for G
@@ -4687,8 +4844,8 @@ void with_sub_block(int slot, F&& f) {
     f(std::integral_constant<uint32_t, SUB_BLOCKS[1]>{});
 }
 
-// The block-wise encoders (coalac_encode_block, _sr, _ef, _g), checks and launch: the call's Params, then
-// k(P, b, delta, x) with the code width, delta mode and the XCD-aware order as constants — the entry point names its
+// The block-wise encoders (coalac_encode_block, _sr, _ef, _g, _rot, _rot_sr), checks and launch: the call's Params,
+// then k(P, b, delta, x) with the code width, delta mode and the XCD-aware order as constants — the entry point names its
 // kernel there and appends its own arguments. ef: d_resid is required too, and read and written 16 bytes at a time.
 template <typename K>
 int block_encode(const char* who, const char* hint, coalac_plan_t plan, const float* d_in, const float* const* d_seg_in,
@@ -4709,12 +4866,13 @@ int block_encode(const char* who, const char* hint, coalac_plan_t plan, const fl
   return launched();
 }
 
-// The stream decoders (coalac_decode_packed, coalac_decode_block, coalac_decode_block_g), checks and launch:
-// k_dense_deq_stream with one range per segment or (per_unit) per unit, or (slot >= 0) k_dense_deq_stream_g with one
-// per block of SUB_BLOCKS[slot] elements. The per-segment ranges are coalac_decode's: their alignment is not tested.
+// The stream decoders (coalac_decode_packed, coalac_decode_block, _g, _rot), checks and launch:
+// k_dense_deq_stream with one range per segment or (per_unit) per unit, (slot >= 0) k_dense_deq_stream_g with one
+// per block of SUB_BLOCKS[slot] elements, or (rot_seed) k_dense_deq_stream_rot, per unit, with the inverse rotation.
+// The per-segment ranges are coalac_decode's: their alignment is not tested.
 int decode_stream(const char* who, coalac_plan_t plan, int slot, bool per_unit, const void* d_packed,
                   uint64_t packed_bytes, const float* d_mn, const float* d_scale, const float* d_base, float* d_out,
-                  void* stream) {
+                  void* stream, const uint64_t* rot_seed = nullptr) {
   const bool blocks = per_unit || slot >= 0;
   bool done = false;
   int rc = dense_stream_args(plan, {who, !d_packed || !d_mn || !d_scale || !d_out ? A_POINTER : nullptr, packed_bytes,
@@ -4727,7 +4885,15 @@ int decode_stream(const char* who, coalac_plan_t plan, int slot, bool per_unit, 
   P.out = d_out;
   const uint32_t bits = (uint32_t)plan->bits, *packed = static_cast<const uint32_t*>(d_packed);
   const bool hb = d_base != nullptr, xcd = !plan->decode_latency;
-  if (slot < 0)
+  if (rot_seed)  // (per unit)
+    with_code_bits(
+        bits,
+        [&](auto b, auto h, auto x) {
+          launch_units(P, stream, k_dense_deq_stream_rot<b.value, h.value, x.value>, plan->dense_pw, packed, d_mn,
+                       d_scale, *rot_seed);
+        },
+        hb, xcd);
+  else if (slot < 0)
     with_code_bits(
         bits,
         [&](auto b, auto pu, auto h, auto x) {
@@ -5250,6 +5416,33 @@ int coalac_encode_block_ef(coalac_plan_t plan, const float* d_in, const float* c
 int coalac_decode_block(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_bmn,
                         const float* d_bscale, const float* d_base, float* d_out, void* stream) {
   return decode_stream("coalac_decode_block", plan, -1, true, d_packed, packed_bytes, d_bmn, d_bscale, d_base, d_out, stream);
+}
+
+int coalac_encode_block_rot(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                            float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t rot_seed,
+                            void* stream) {
+  return block_encode("coalac_encode_block_rot", PACK_HINT, plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed,
+                      packed_bytes, [&](const Params& P, auto b, auto delta, auto x) {
+                        launch_units(P, stream, k_dense_block_quant_rot<delta.value, b.value, x.value, false>,
+                                     plan->dense_pw, d_bmn, d_bscale, static_cast<uint32_t*>(d_packed), rot_seed,
+                                     (uint64_t)0);
+                      });
+}
+
+int coalac_encode_block_rot_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                               float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t rot_seed,
+                               uint64_t seed, void* stream) {
+  return block_encode("coalac_encode_block_rot_sr", SR_HINT, plan, d_in, d_seg_in, d_base, d_bmn, d_bscale, d_packed,
+                      packed_bytes, [&](const Params& P, auto b, auto delta, auto x) {
+                        launch_units(P, stream, k_dense_block_quant_rot<delta.value, b.value, x.value, true>,
+                                     plan->dense_pw, d_bmn, d_bscale, static_cast<uint32_t*>(d_packed), rot_seed, seed);
+                      });
+}
+
+int coalac_decode_block_rot(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_bmn,
+                            const float* d_bscale, uint64_t rot_seed, const float* d_base, float* d_out, void* stream) {
+  return decode_stream("coalac_decode_block_rot", plan, -1, true, d_packed, packed_bytes, d_bmn, d_bscale, d_base, d_out,
+                       stream, &rot_seed);
 }
 
 int coalac_plan_block_count(coalac_plan_t plan, uint32_t block, uint64_t* n_blocks) {

@@ -397,6 +397,39 @@ int coalac_aggregate_dense_g(coalac_plan_t plan, int clients, uint32_t block, co
                              const float* d_weights, float total, int mode, const uint8_t* d_avg_mask,
                              const float* d_base, float* d_out, void* stream);
 
+/* Rotated block-wise quantisation (an addition to CodecSpec v1, bit for bit; additive symbols, the ABI
+ * version does not step). `plan` is a dense plan (every k == n), bits 1..8. Unit u — the u_s-th of segment s, `len`
+ * elements, its first at flat position c0 = in_off_s + 4096 u_s — is
+ *
+ *   len < 4096   not rotated: exactly coalac_encode_block / coalac_encode_block_sr / coalac_decode_block (a ragged last
+ *                unit, every small tensor). Which units are rotated is a function of the plan alone.
+ *   len == 4096  a[e] = x[e] (- base[e], fp32); s[e] = a[e] with its sign bit inverted where bit 23 of the 24-bit draw of
+ *                position c0 + e under `rot_seed` is set (the hash of coalac_encode_sr's contract; an XOR on the bit
+ *                pattern, also of +-0, +-Inf and NaN); then for h = 1, 2, 4, ..., 2048, in this order, every pair
+ *                (i, i + h) with i & h == 0 becomes (t[i] + t[i+h], t[i] - t[i+h]), all fp32, and y[e] = t[e] * 2^-6 (the
+ *                orthonormal Walsh-Hadamard transform). y is quantised exactly as coalac_encode_block quantises x: bmn[u],
+ *                bscale[u] from its NaN-ignoring min / max, the round-to-nearest code, or (_rot_sr) the stochastic code
+ *                of coalac_encode_block_sr with the draw of position c0 + e under `seed`.
+ *   decode       yq[e] = bmn[u] + float(code) * bscale[u] (multiply, then add); the same transform and * 2^-6, the same
+ *                sign inversion, + base[e] when given. The transform and the signs are their own inverses, so the error of
+ *                the decoded unit is the quantisation error of y, rotated.
+ *   code stream  wire v4's, unchanged in layout and length; d_bmn / d_bscale: fp32[n_units]
+ *
+ * bmn, bscale and the stream are bit-exact against the host model for any input, non-finite values included (every
+ * intermediate's class follows from IEEE add and subtract); decoded values too, except that a NaN's sign and payload are
+ * not specified. A stream decoded with another rot_seed, or without the rotation, is wrong but never out of bounds.
+ * Arguments, sizes, alignment and COALAC_EINVAL cases are the twins' (coalac_encode_block, coalac_encode_block_sr,
+ * coalac_decode_block), all checked before the first device call; a plan without units returns COALAC_OK and launches
+ * nothing. Each call is one asynchronous launch on `stream`: no allocation, no workspace, no host synchronisation. */
+int coalac_encode_block_rot(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                            float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t rot_seed,
+                            void* stream);
+int coalac_encode_block_rot_sr(coalac_plan_t plan, const float* d_in, const float* const* d_seg_in, const float* d_base,
+                               float* d_bmn, float* d_bscale, void* d_packed, uint64_t packed_bytes, uint64_t rot_seed,
+                               uint64_t seed, void* stream);
+int coalac_decode_block_rot(coalac_plan_t plan, const void* d_packed, uint64_t packed_bytes, const float* d_bmn,
+                            const float* d_bscale, uint64_t rot_seed, const float* d_base, float* d_out, void* stream);
+
 /* coalac_aggregate from each SPARSE upload's own buffers. `plan` is a ONE-LAYOUT sparse plan (not dense;
  * bits 1..8 or 32): d_out / d_base are indexed by its in_off. The arithmetic is coalac_aggregate's contract bit for bit
  * (x_i = base + d_i, +0.0f where client i kept nothing; acc = x_0 * w_0, acc = acc + x_i * w_i in client order, no FMA;
